@@ -11,6 +11,15 @@ Workload semantics follow the reference's scripts/benchmarks/measure_throughput.
     `--mode physics` times decimation x Simulation.step only (measure_physics_sps).
 Actions are uniform[-1,1) from a torch Generator seeded 0 (scripts/play.py:173-176).
 
+A plain run sets up, warms up, times the K steps and prints the line; its `roofline` is
+arithmetic on the timed region's own HIP events, and `roofline.single_launch_ms` and
+`cpu_baseline` are null.  `--full` adds the legs that take runs of their own: the
+`--launch-reps` single steps timed one by one, and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned to its caller, as
+DIR/<name>.npy in float32: in env mode obs_<group>, reward, terminated and truncated of
+env.step; in physics mode qpos, qvel and qacc of the simulation.  The env seed and the
+action generator's seed are fixed, so the same arguments give the same inputs every run.
+
 roofline: the dominant "kernel" is one env step exactly as the timed region runs it (the
 HIP graph of decimation x physics phases A/B/C + the fused manager kernels); algorithmic
 bytes per env-step B_env = 4*[dec*(2nq+5nv+2nu+ns+1) + 16*nbody + 72] (SURVEY.md section
@@ -26,9 +35,9 @@ contact work past the max capacity); non-zero makes the run exit 3 after printin
 (--allow-overflow).  resolved_events: world-substeps that overflowed the fast LDS carve and
 were re-solved at the max capacity inside the same step (nothing dropped; their cost is in
 the timing).
-cpu_baseline: the fp64 CPU oracle (oracle/liboracle.so, "port") on the allotted host cores
-over the bench's own worlds with random actions, plus config 1 (num_envs=1, zero action,
-one thread).
+cpu_baseline (--full): the fp64 CPU oracle (oracle/liboracle.so, "port") on the allotted host
+cores over the bench's own worlds with random actions, plus config 1 (num_envs=1, zero
+action, one thread).
 """
 
 from __future__ import annotations
@@ -210,6 +219,29 @@ def reduce_over_ranks(el: float, dropped, stats: torch.Tensor, device):
   return el, dropped, gather.wait()
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, rank: int = 0) -> None:
+  """`--dump-outputs`: write {name: tensor} as path/<name>.npy in float32 (rank r > 0 of a
+  multi-GPU run writes <name>_rank<r>.npy).  Arrays whose sum would pass DUMP_BYTES_MAX are
+  cut to a fixed sample of their rows (worlds), drawn from a generator seeded 0 and kept in
+  order, the same rows for every array of that length."""
+  os.makedirs(path, exist_ok=True)
+  host = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in arrays.items()}
+  total = sum(a.nbytes for a in host.values())
+  if total > DUMP_BYTES_MAX:
+    rows = {}
+    for k, a in host.items():
+      n = a.shape[0]
+      if n not in rows:
+        keep = max(1, int(n * DUMP_BYTES_MAX / total))
+        rows[n] = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+      host[k] = np.ascontiguousarray(a[rows[n]])
+  for k, a in host.items():
+    np.save(os.path.join(path, k + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def _launch_ranks(args_gpus: int) -> int:
   """`bench.py --gpus N` started without a launcher: start the N ranks through
   torch.distributed.run (one process per GPU, 127.0.0.1 rendezvous) before this process
@@ -233,7 +265,13 @@ def main():
   ap.add_argument("--num-envs", type=int, default=4096)
   ap.add_argument("--task", default="Mjlab-Velocity-Flat-Unitree-G1")
   ap.add_argument("--mode", choices=["env", "physics"], default="env")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="also run the legs beside the headline figure: --launch-reps single "
+                       "steps timed one by one, and the CPU baseline")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step returned as DIR/<name>.npy (float32)")
+  ap.add_argument("--no-cpu-baseline", action="store_true",
+                  help="with --full: skip the CPU baseline leg")
   ap.add_argument("--eager", action="store_true", help="reference-style eager env.step (host syncs)")
   ap.add_argument("--launch-reps", type=int, default=20,
                   help="env steps timed one by one with HIP events after the timed region")
@@ -299,7 +337,7 @@ def main():
 
   def one_step(a):
     if args.mode == "env":
-      env.step(a)
+      return env.step(a)
     else:
       env.action_manager.process_action(a)
       for _ in range(dec):
@@ -307,6 +345,7 @@ def main():
         env.scene.write_data_to_sim()
         sim.step()
 
+  last = None
   for _ in range(args.warmup):
     one_step(draw())
   ev_before = sim.event_counts().clone()
@@ -322,7 +361,7 @@ def main():
   t0 = time.perf_counter()
   r0.record(stream)
   for _ in range(args.steps):
-    one_step(draw())
+    last = one_step(draw())
   r1.record(stream)
   torch.cuda.synchronize()
   if dist is not None:
@@ -334,19 +373,30 @@ def main():
   # re-solves of worlds that overflowed the fast carve
   events = (sim.event_counts() - ev_before).cpu().tolist()
   region_ms = r0.elapsed_time(r1) / args.steps
-  # and, for reference, HIP events around each of `launch_reps` further single steps on the
-  # stream they are launched on (torch's current stream; graph replays and the engine's
-  # launches both go there): isolated replays, no overlap with a neighbour
-  acts = [draw() for _ in range(args.launch_reps)]
-  pairs = []
-  for a in acts:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    one_step(a)
-    e1.record(stream)
-    pairs.append((e0, e1))
-  torch.cuda.synchronize()
-  single_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in pairs]))
+  if args.dump_outputs:
+    # before anything steps the env again: the graph path returns the same buffers every step
+    if args.mode == "env" and last is not None:
+      obs, rew, term, trunc = last[:4]
+      arrays = {f"obs_{k}": v for k, v in obs.items()}
+      arrays.update(reward=rew, terminated=term, truncated=trunc)
+    else:
+      arrays = {"qpos": sim.data.qpos, "qvel": sim.data.qvel, "qacc": sim.data.qacc}
+    dump_outputs(args.dump_outputs, arrays, rank)
+  single_ms = None
+  if args.full:
+    # and, for reference, HIP events around each of `launch_reps` further single steps on the
+    # stream they are launched on (torch's current stream; graph replays and the engine's
+    # launches both go there): isolated replays, no overlap with a neighbour
+    acts = [draw() for _ in range(args.launch_reps)]
+    pairs = []
+    for a in acts:
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record(stream)
+      one_step(a)
+      e1.record(stream)
+      pairs.append((e0, e1))
+    torch.cuda.synchronize()
+    single_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in pairs]))
   launch_ms = float(region_ms)
   st = sim.stats()
   if dist is not None:
@@ -412,7 +462,7 @@ def main():
                    "limiter": (prof or {}).get("limiter", "latency/VALU issue (not HBM)")},
       "cpu_baseline": None,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
       out["cpu_baseline"] = cpu_baseline(env, dec)
     print(json.dumps(out), flush=True)
   if dist is not None:

@@ -8,7 +8,7 @@ run() {
   grep '^{' "gpurun_out/bench_$1.log" | tail -1 > "gpurun_out/bench_$1.json"
   python3 -c "import json; d=json.load(open('gpurun_out/bench_$1.json')); print('$1', $2, round(d['value']), 'env-steps/s', round(d['ms_per_step'], 3), 'ms/step')"
 }
-run Mjlab-Velocity-Flat-Unitree-G1 4096 200
+run Mjlab-Velocity-Flat-Unitree-G1 4096 200 --full
 run Mjlab-Velocity-Flat-Unitree-Go1 8192 200 --no-cpu-baseline
 run Mjlab-Tracking-Flat-Unitree-G1 4096 100 --no-cpu-baseline
 run Mjlab-Jump-Flat-Unitree-G1 16384 60 --no-cpu-baseline

@@ -17,7 +17,7 @@ OUT=gpurun_out/prof_${TAG}
 SQ=${SQ:-"SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM"}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="bench.py --task $TASK --num-envs $NENV --steps $STEPS --warmup 5 --launch-reps 4 --no-cpu-baseline --allow-overflow"
+B="bench.py --task $TASK --num-envs $NENV --steps $STEPS --warmup 5 --full --launch-reps 4 --no-cpu-baseline --allow-overflow"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/kt" -o kt -- python3 $B \
   > "$OUT/bench_prof.log" 2>&1
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -f csv -d "$OUT/fetch" -o fetch -- python3 $B \
