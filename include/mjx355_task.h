@@ -17,9 +17,10 @@
  *                         reset_joints_by_offset), action/command/event manager resets
  *                         (manager_based_rl_env.py:381-416, envs/mdp/events.py:81-206)
  *   mjx_task_observe   <- CommandManager.compute, EventManager.apply("interval"),
- *                         ObservationManager.compute (command_manager.py:53-67,
- *                         velocity_command.py:51-107, event_manager.py:124-146,
- *                         observation_manager.py:154-208)
+ *                         ObservationManager.compute with per-term history and delay
+ *                         (command_manager.py:53-67, velocity_command.py:51-107,
+ *                         event_manager.py:124-146, observation_manager.py:154-208;
+ *                         mjxObsState below)
  *
  * The same kernels run the jump task (command_kind MJX_CMD_JUMP: JumpCommand,
  * tasks/jump/mdp/commands.py:17-62; its reward / termination kinds and observation layout,
@@ -46,6 +47,54 @@ extern "C" {
 #define MJX_TASK_MAX_FEET 8
 #define MJX_TASK_MAX_TERMS 24
 #define MJX_TASK_MAX_CONTACT_SLOTS 32
+#define MJX_TASK_MAX_OBS_TERMS 16  /* observation terms per group */
+#define MJX_TASK_MAX_HISTORY 32    /* ObservationTermCfg.history_length */
+#define MJX_TASK_MAX_LAG 15        /* ObservationTermCfg.delay_max_lag */
+
+/* Observation history and delay (observation_manager.py:189-207, utils/buffers/): the last
+ * fields of mjxTaskDesc and mjxTrackDesc.  All zero = no history, no delay, and the observe
+ * kernels write exactly the single-frame rows [nworld, npolicy] / [nworld, ncritic].
+ *
+ * Otherwise each group (0 policy, 1 critic) carries one segment per observation term of the
+ * task's fixed layout, in layout order.  A term of width w and history H (0 = none) owns
+ * max(H, 1) * w consecutive floats of the group row, frames oldest first: the flattened
+ * term-major layout of the reference, so npolicy / ncritic = sum w * max(H, 1).  The output
+ * tensor is the storage: every observe moves the term's block down by one frame and writes
+ * the new frame last (the thread that computes element j of the frame moves column j of
+ * the older frames, so no thread reads what another writes).  Older policy frames keep the
+ * noise they were written with.
+ *
+ * fresh[e] != 0 makes the next observe write env e's new frame to all H slots (the first
+ * append after a reset).  The reset kernels set it for the masked envs; observe clears it
+ * after every thread of the env has read it (velocity / jump: the env's wave, after its
+ * element loop; tracking: a launch that follows the observation kernel).  A second observe
+ * with no step in between therefore appends a second frame, as a second
+ * compute(update_history=True) does.
+ *
+ * A term with max_lag > 0 is delayed before it enters its history block: ring
+ * [nworld, max_lag + 1, w] (oldest first, shifted like a history block and backfilled when
+ * delay_pushes[e] == 0), the lag drawn per env and per step, uniform in [min_lag, max_lag]
+ * from the counter hash (the reference's distribution, not its stream) and clamped to the
+ * frames the env holds; delay_lag [2 * MJX_TASK_MAX_OBS_TERMS, nworld] receives the lag
+ * used (row = group * MJX_TASK_MAX_OBS_TERMS + term).  The reset kernels zero delay_pushes
+ * and the lags of the masked envs.  Other lag policies (update period, hold probability,
+ * shared lag) are not implemented here. */
+typedef struct mjxObsSeg_ {
+  int width, history, min_lag, max_lag;
+} mjxObsSeg;
+typedef struct mjxObsGroup_ {
+  int nterm;                                   /* 0 = no table */
+  int frame;                                   /* set by create: sum of widths */
+  mjxObsSeg seg[MJX_TASK_MAX_OBS_TERMS];
+  int out_off[MJX_TASK_MAX_OBS_TERMS];         /* set by create: the term's first float */
+  float* delay_ring[MJX_TASK_MAX_OBS_TERMS];   /* per delayed term, else null */
+} mjxObsGroup;
+typedef struct mjxObsState_ {
+  mjxObsGroup group[2];                        /* policy, critic */
+  uint8_t* fresh;                              /* [nworld] */
+  int32_t* delay_pushes;                       /* [nworld] */
+  int32_t* delay_lag;                          /* [2 * MJX_TASK_MAX_OBS_TERMS, nworld] */
+} mjxObsState;
 
 /* reward term kinds (tasks/velocity/mdp/rewards.py, envs/mdp/rewards.py) */
 enum { MJX_RW_TRACK_LIN = 0, MJX_RW_TRACK_ANG = 1, MJX_RW_FLAT_ORIENT = 2, MJX_RW_POSE = 3,
@@ -146,6 +195,8 @@ typedef struct mjxTaskDesc_ {
   uint8_t* jump_initialized;
   float* landing_timer;                    /* landing_balance state [nworld] */
   uint8_t* was_in_air;
+  /* ---- observation history / delay (all zero: none) */
+  mjxObsState obs;
 } mjxTaskDesc;
 
 typedef struct mjxTask_ mjxTask;
@@ -272,6 +323,8 @@ typedef struct mjxTrackDesc_ {
   float *obs_policy, *obs_critic;
   float *log_reward, *log_termination, *log_metric; /* [nreward] [ntermination] [NMETRIC] */
   uint64_t* step_counter;
+  /* ---- observation history / delay (all zero: none) */
+  mjxObsState obs;
 } mjxTrackDesc;
 
 typedef struct mjxTrack_ mjxTrack;

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/mjx355_task.h"
+#include "obs_hist.h"
 
 namespace mjtr {
 
@@ -424,6 +425,7 @@ __global__ __launch_bounds__(64 * kPostEnvs) void k_rsi(const mjxTrackDesc* __re
     if (t.has_push)
       t.push_time_left[e] = uniform(t.push_interval[0], t.push_interval[1], urand(seed, e, step, D_PUSH + 15));
     t.episode_length[e] = 0;
+    mjxobs::reset_env(t.obs, e, t.nworld);
     // CommandTerm._resample_masked: timer and counter (the motion-end resample of
     // _update_command calls _resample_command directly, without them)
     t.command_counter[e] += 1;
@@ -543,7 +545,7 @@ __global__ __launch_bounds__(64 * kPostEnvs) void k_targets(const mjxTrackDesc* 
 __global__ void k_obs(const mjxTrackDesc* __restrict__ T) {
   const mjxTrackDesc& t = *T;
   const int nj = t.njoint, nmb = t.nmb;
-  const int nel = t.ncritic;
+  const int nel = t.obs.group[1].nterm ? t.obs.group[1].frame : t.ncritic;  // the critic's frame
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= t.nworld * nel) return;
   const int e = idx / nel;
@@ -613,12 +615,23 @@ __global__ void k_obs(const mjxTrackDesc* __restrict__ T) {
     val = t.action[(size_t)e * nj + i - o_act];
     pol = p_act + i - o_act; pol_val = val;
   }
-  t.obs_critic[(size_t)e * nel + i] = val;
-  if (pol >= 0) {
-    if (t.corrupt_policy && noise > 0.f)
-      pol_val += uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + pol));
-    t.obs_policy[(size_t)e * t.npolicy + pol] = pol_val;
+  if (pol >= 0 && t.corrupt_policy && noise > 0.f)
+    pol_val += uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + pol));
+  if (t.obs.group[1].nterm == 0) {
+    t.obs_critic[(size_t)e * nel + i] = val;
+    if (pol >= 0) t.obs_policy[(size_t)e * t.npolicy + pol] = pol_val;
+    return;
   }
+  // with a segment table (mjxObsState): through the terms' delay rings into their history blocks
+  auto draw = [&](uint32_t id) { return urand(t.seed, e, *t.step_counter, id); };
+  mjxobs::store(t.obs, 1, t.obs_critic + (size_t)e * t.ncritic, e, t.nworld, i, val, draw);
+  if (pol >= 0) mjxobs::store(t.obs, 0, t.obs_policy + (size_t)e * t.npolicy, e, t.nworld, pol, pol_val, draw);
+}
+// after k_obs (a launch boundary: every thread of every env has read the fresh flags and push
+// counts): the envs' frames are stored, the next observe appends
+__global__ void k_obs_done(const mjxTrackDesc* __restrict__ T) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < T->nworld) mjxobs::frame_done(T->obs, e);
 }
 
 // episode logs of the step's resets (k_post's accumulators), then cleared
@@ -753,8 +766,9 @@ int mjx_track_create(const mjxTrackDesc* d, mjxTrack** out) {
       d->kernel_size > 8 || d->nframe < 1)
     return track_fail("tracking descriptor exceeds compiled capacities");
   const int nj = d->njoint, nmb = d->nmb;
-  if (d->ncritic != 5 * nj + 9 * nmb + 15 ||
-      d->npolicy != 5 * nj + 9 + (d->policy_anchor_pos ? 3 : 0) + (d->policy_lin_vel ? 3 : 0))
+  const int frame[2] = {5 * nj + 9 + (d->policy_anchor_pos ? 3 : 0) + (d->policy_lin_vel ? 3 : 0),
+                        5 * nj + 9 * nmb + 15};
+  if (!mjxobs::enabled(d->obs) && (d->ncritic != frame[1] || d->npolicy != frame[0]))
     return track_fail("observation sizes do not match the tracking layout");
   {
     const std::string why = validate_track(*d);
@@ -762,6 +776,15 @@ int mjx_track_create(const mjxTrackDesc* d, mjxTrack** out) {
   }
   auto* t = new mjxTrack_();
   t->host = *d;
+  {
+    // segment tables against the layout's frames; fills their derived offsets
+    const int width[2] = {d->npolicy, d->ncritic};
+    const std::string why = mjxobs::prepare(t->host.obs, frame, width);
+    if (!why.empty()) {
+      delete t;
+      return track_fail("mjx_track_create: " + why);
+    }
+  }
   t->nworld = d->nworld;
   if (hipMalloc((void**)&t->dev, sizeof(mjxTrackDesc)) != hipSuccess ||
       hipMalloc((void**)&t->part, sizeof(float) * mjtr::kAccN *
@@ -769,7 +792,7 @@ int mjx_track_create(const mjxTrackDesc* d, mjxTrack** out) {
     delete t;
     return track_fail("hipMalloc failed");
   }
-  if (hipMemcpy(t->dev, d, sizeof(mjxTrackDesc), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(t->dev, &t->host, sizeof(mjxTrackDesc), hipMemcpyHostToDevice) != hipSuccess) {
     delete t;
     return track_fail("upload failed");
   }
@@ -822,8 +845,11 @@ int mjx_track_observe(mjxTrack* t, void* stream) {
   hipLaunchKernelGGL(mjtr::k_rsi, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev,
                      (const uint8_t*)t->host.resample_mask, 0, (uint32_t)mjtr::D_CMD_SAMPLE);
   hipLaunchKernelGGL(mjtr::k_targets, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev);
-  const long n = (long)t->nworld * t->host.ncritic;
+  const bool hist = mjxobs::enabled(t->host.obs);
+  const long n = (long)t->nworld * (hist ? t->host.obs.group[1].frame : t->host.ncritic);
   hipLaunchKernelGGL(mjtr::k_obs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->dev);
+  if (hist)
+    hipLaunchKernelGGL(mjtr::k_obs_done, dim3((unsigned)((t->nworld + 255) / 256)), dim3(256), 0, s, t->dev);
   return track_launched("k_obs");
 }
 

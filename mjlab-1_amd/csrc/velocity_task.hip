@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/mjx355_task.h"
+#include "obs_hist.h"
 
 namespace mjxt {
 
@@ -676,6 +677,7 @@ __global__ void k_reset(const mjxTaskDesc* __restrict__ T) {
   if (t.has_push)
     t.push_time_left[e] = uniform(t.push_interval[0], t.push_interval[1], urand(seed, e, step, D_CMD_RESET + 16));
   t.episode_length[e] = 0;
+  mjxobs::reset_env(t.obs, e, t.nworld);
 }
 
 // logs of the previous kernels' reductions (k_post ran to completion before this launch)
@@ -749,11 +751,28 @@ __device__ void observe_env(const mjxTaskDesc& t, int e) {
 // jump layout (tasks/jump/jump_env_cfg.py:61-110): policy = [lin 3, ang 3, gravity 3, jpos,
 // jvel, actions, height 1, vertical velocity 1, contact nf, air time nf, command 1]; critic =
 // policy terms + [foot height nf, sign*log1p|force| 3nf]
+// Element i of the critic's frame (and, for the shared head, of the policy's, plus noise) into
+// the group rows: the single-frame rows, or with a segment table (mjxObsState) the terms'
+// delay rings and history blocks.
+__device__ __forceinline__ void obs_put(const mjxTaskDesc& t, int e, int i, float val, bool in_policy,
+                                        bool noisy, float noise) {
+  const float pv = noisy ? val + uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + i)) : val;
+  float* co = t.obs_critic + (size_t)e * t.ncritic;
+  float* po = t.obs_policy + (size_t)e * t.npolicy;
+  if (t.obs.group[1].nterm == 0) {
+    co[i] = val;
+    if (in_policy) po[i] = pv;
+    return;
+  }
+  auto draw = [&](uint32_t id) { return urand(t.seed, e, *t.step_counter, id); };
+  mjxobs::store(t.obs, 1, co, e, t.nworld, i, val, draw);
+  if (in_policy) mjxobs::store(t.obs, 0, po, e, t.nworld, i, pv, draw);
+}
+
 __device__ __forceinline__ void obs_jump(const mjxTaskDesc& t, int e, int i) {
   const int nj = t.njoint, nf = t.nfeet;
   const int nput = 9 + 3 * nj + 2 + 2 * nf + 1;
   const float* sd = t.sensordata + (size_t)e * t.nsensordata;
-  float* co = t.obs_critic + (size_t)e * t.ncritic;
   if (i < nput) {
     float val, noise = 0.f;
     if (i < 3) {
@@ -786,9 +805,7 @@ __device__ __forceinline__ void obs_jump(const mjxTaskDesc& t, int e, int i) {
         val = t.command[e];
       }
     }
-    co[i] = val;
-    t.obs_policy[(size_t)e * t.npolicy + i] =
-        t.corrupt_policy && noise > 0.f ? val + uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + i)) : val;
+    obs_put(t, e, i, val, true, t.corrupt_policy && noise > 0.f, noise);
     return;
   }
   const int x = i - nput;
@@ -800,12 +817,12 @@ __device__ __forceinline__ void obs_jump(const mjxTaskDesc& t, int e, int i) {
     const float fv = sd[t.feet_force_adr[fs] + k];
     v = copysignf(log1pf(fabsf(fv)), fv) * (fv != 0.f ? 1.f : 0.f);
   }
-  co[i] = v;
+  obs_put(t, e, i, v, false, false, 0.f);
 }
 
 // observation elements of env e: the critic's (the jump layout, or the velocity layout)
 __device__ __forceinline__ int obs_count(const mjxTaskDesc& t) {
-  if (t.command_kind == MJX_CMD_JUMP) return t.ncritic;
+  if (t.command_kind == MJX_CMD_JUMP) return t.obs.group[1].nterm ? t.obs.group[1].frame : t.ncritic;
   const int nput = 9 + 3 * t.njoint + 3;
   return t.critic_extras ? nput + 6 * t.nfeet : nput;
 }
@@ -817,7 +834,6 @@ __device__ void obs_elem(const mjxTaskDesc& t, int e, int i) {
   const int nj = t.njoint;
   const int nput = 9 + 3 * nj + 3;  // elements shared by the policy and critic groups
   const float* sd = t.sensordata + (size_t)e * t.nsensordata;
-  float* co = t.obs_critic + (size_t)e * t.ncritic;
   if (i < nput) {
     float val, noise = 0.f;
     if (i < 3) {
@@ -839,10 +855,8 @@ __device__ void obs_elem(const mjxTaskDesc& t, int e, int i) {
     } else {
       val = t.command[(size_t)e * 3 + i - 9 - 3 * nj];
     }
-    co[i] = val;
     const bool noisy = t.corrupt_policy != 0;
-    t.obs_policy[(size_t)e * t.npolicy + i] =
-        noisy && noise > 0.f ? val + uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + i)) : val;
+    obs_put(t, e, i, val, true, noisy && noise > 0.f, noise);
     return;
   }
   const int x = i - nput, nf = t.nfeet, s = x % nf, blk = x / nf;
@@ -858,7 +872,7 @@ __device__ void obs_elem(const mjxTaskDesc& t, int e, int i) {
     const float fv = sd[t.feet_force_adr[fs] + k];
     v = copysignf(log1pf(fabsf(fv)), fv) * (fv != 0.f ? 1.f : 0.f);
   }
-  co[i] = v;
+  obs_put(t, e, i, v, false, false, 0.f);
 }
 
 // Command update, interval events and observations as one launch, a wave per env: lane 0
@@ -912,6 +926,12 @@ __global__ __launch_bounds__(64 * kObsEnvs, 8) void k_observe_obs(const mjxTaskD
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   const int nel = obs_count(t);
   for (int i = lane; i < nel; i += 64) obs_elem(t, e, i);
+  if (t.obs.group[1].nterm) {
+    // every lane of the env's wave has read the fresh flag and the push count (their values
+    // steered the stores above); only now does lane 0 advance them
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) mjxobs::frame_done(t.obs, e);
+  }
 }
 
 // Terrain-level curriculum over the reset mask (tasks/velocity/mdp/curriculums.py:30-64,
@@ -995,7 +1015,7 @@ size_t mjx_task_desc_size(void) { return sizeof(mjxTaskDesc); }
 // the device: a mismatch is an error code and mjx_task_last_error, never an out-of-bounds
 // access on the GPU (round 5: a twist-command read on the jump task's [nworld, 1] command
 // faulted the device).  Returns "" when the descriptor is consistent.
-static std::string validate_task(const mjxTaskDesc& t) {
+static std::string validate_task(mjxTaskDesc& t) {
   auto in = [](int v, int n) { return v >= 0 && v < n; };
   auto span = [](int adr, int len, int n) { return adr >= 0 && adr + len <= n; };
   char buf[256];
@@ -1102,17 +1122,25 @@ static std::string validate_task(const mjxTaskDesc& t) {
       return err("termination %d: illegal_contact with no contact slots (%d)", k, t.nillegal);
   }
   // observation layouts (k_observe_obs writes exactly these widths)
+  // without a segment table; with one, the rows are the terms' history blocks over the same
+  // frames (mjxobs::prepare also fills the table's derived offsets)
   const int nj = t.njoint, nf = t.nfeet;
+  int frame[2];
   if (t.command_kind == MJX_CMD_JUMP) {
-    if (t.npolicy != 9 + 3 * nj + 3 + 2 * nf || t.ncritic != t.npolicy + 4 * nf)
+    frame[0] = 9 + 3 * nj + 3 + 2 * nf;
+    frame[1] = frame[0] + 4 * nf;
+    if (!mjxobs::enabled(t.obs) && (t.npolicy != frame[0] || t.ncritic != frame[1]))
       return err("observation widths (%d, %d) do not match the jump task layout", t.npolicy, t.ncritic);
   } else {
     const int nput = 9 + 3 * nj + 3;
-    if (t.npolicy != nput || t.ncritic != nput + (t.critic_extras ? 6 * nf : 0))
+    frame[0] = nput;
+    frame[1] = nput + (t.critic_extras ? 6 * nf : 0);
+    if (!mjxobs::enabled(t.obs) && (t.npolicy != frame[0] || t.ncritic != frame[1]))
       return err("observation widths (%d, %d) do not match the velocity task layout", t.npolicy, t.ncritic);
     if (t.critic_extras && nf == 0) return "critic_extras with no feet";
   }
-  return "";
+  const int width[2] = {t.npolicy, t.ncritic};
+  return mjxobs::prepare(t.obs, frame, width);
 }
 
 extern "C" {
@@ -1123,12 +1151,15 @@ int mjx_task_create(const mjxTaskDesc* desc, mjxTask** out) {
       desc->nreward > MJX_TASK_MAX_TERMS || desc->ntermination > MJX_TASK_MAX_TERMS ||
       desc->nillegal > MJX_TASK_MAX_CONTACT_SLOTS)
     return task_fail("task descriptor exceeds compiled capacities");
-  {
-    const std::string why = validate_task(*desc);
-    if (!why.empty()) return task_fail("mjx_task_create: " + why);
-  }
   auto* t = new mjxTask_();
   t->host = *desc;
+  {
+    const std::string why = validate_task(t->host);
+    if (!why.empty()) {
+      delete t;
+      return task_fail("mjx_task_create: " + why);
+    }
+  }
   t->nworld = desc->nworld;
   const size_t nblock = ((size_t)t->nworld + mjxt::kPostEnvs - 1) / mjxt::kPostEnvs;
   if (hipMalloc((void**)&t->dev, sizeof(mjxTaskDesc)) != hipSuccess ||
@@ -1143,7 +1174,7 @@ int mjx_task_create(const mjxTaskDesc* desc, mjxTask** out) {
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
       t->ncu = ncu;
   }
-  if (hipMemcpy(t->dev, desc, sizeof(mjxTaskDesc), hipMemcpyHostToDevice) != hipSuccess ||
+  if (hipMemcpy(t->dev, &t->host, sizeof(mjxTaskDesc), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(t->acc, 0, sizeof(mjxt::Acc)) != hipSuccess) {
     delete t;
     return task_fail("upload failed");
@@ -1201,7 +1232,9 @@ int mjx_task_observe(mjxTask* t, void* stream) {
   if (!t) return task_fail("null task");
   const int nj = t->host.njoint, nf = t->host.nfeet;
   int nel;
-  if (t->host.command_kind == MJX_CMD_JUMP) {
+  if (mjxobs::enabled(t->host.obs)) {  // rows checked against the segment tables at create
+    nel = t->host.obs.group[1].frame;
+  } else if (t->host.command_kind == MJX_CMD_JUMP) {
     nel = t->host.ncritic;
     if (t->host.npolicy != 9 + 3 * nj + 3 + 2 * nf || nel != t->host.npolicy + 4 * nf)
       return task_fail("observation sizes do not match the jump task layout");

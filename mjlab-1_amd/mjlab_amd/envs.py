@@ -214,7 +214,7 @@ class ManagerBasedRlEnv:
                 self.event_manager, self.termination_manager):
       log.update(mgr.reset_masked(mask))
     self._log_sim_counters(log)
-    self.observation_manager.reset(None)
+    self.observation_manager.reset_masked(mask)
     self.episode_length_buf.masked_fill_(mask, 0)
 
   def _graph_key(self):

@@ -13,6 +13,10 @@ The kernels read and write the managers' own tensors (action histories, command 
 episode sums, termination flags, contact-sensor air times, swing-height peaks), so every
 Python accessor of the reference API keeps working. Episode logs go to device scalars
 that are exposed in `extras["log"]` under the reference's key names.
+
+Observation history and the per-env redrawn delay run in the observe kernels
+(`FusedObsHistory`, the descriptors' `obs` tail); the observation rows are the history
+storage, seeded from and handed back to the manager's buffers.
 """
 
 from __future__ import annotations
@@ -33,6 +37,24 @@ _FP = ctypes.POINTER(ctypes.c_float)
 _U8 = ctypes.POINTER(ctypes.c_uint8)
 _I64 = ctypes.POINTER(ctypes.c_int64)
 _U64 = ctypes.POINTER(ctypes.c_uint64)
+_I32 = ctypes.POINTER(ctypes.c_int32)
+MAX_OBS_TERMS, MAX_HISTORY, MAX_LAG = 16, 32, 15
+
+
+class ObsSeg(ctypes.Structure):
+  """ctypes mirror of mjxObsSeg (include/mjx355_task.h)."""
+  _fields_ = [("width", ctypes.c_int), ("history", ctypes.c_int),
+              ("min_lag", ctypes.c_int), ("max_lag", ctypes.c_int)]
+
+
+class ObsGroup(ctypes.Structure):
+  _fields_ = [("nterm", ctypes.c_int), ("frame", ctypes.c_int), ("seg", ObsSeg * MAX_OBS_TERMS),
+              ("out_off", ctypes.c_int * MAX_OBS_TERMS), ("delay_ring", _FP * MAX_OBS_TERMS)]
+
+
+class ObsState(ctypes.Structure):
+  """ctypes mirror of mjxObsState: the descriptors' observation history / delay tail."""
+  _fields_ = [("group", ObsGroup * 2), ("fresh", _U8), ("delay_pushes", _I32), ("delay_lag", _I32)]
 
 
 class TaskDesc(ctypes.Structure):
@@ -94,6 +116,7 @@ class TaskDesc(ctypes.Structure):
     ("actuator_force", _FP), ("act_ctrl", ctypes.c_int * MAXJ), ("explosive_joints", ctypes.c_uint64),
     ("jump_peak", _FP), ("jump_initial", _FP), ("jump_initialized", _U8),
     ("landing_timer", _FP), ("was_in_air", _U8),
+    ("obs", ObsState),
   ]
 
 
@@ -144,6 +167,109 @@ def _noise(cfg):
 def _range6(spec):
   keys = ["x", "y", "z", "roll", "pitch", "yaw"]
   return [tuple(map(float, (spec or {}).get(k, (0.0, 0.0)))) for k in keys]
+
+
+class FusedObsHistory:
+  """Observation history / delay of a fused step (mjxObsState): fills the descriptor's
+  segment tables from the manager's term configs, owns the device state (fresh flags, delay
+  rings, lags, push counts) and moves that state between the manager's buffers and the
+  kernels' when the env switches paths.
+
+  `groups`: the (name, cfg) term lists of the policy and critic groups, already matched
+  against the task's fixed layout.  `build` returns None (and leaves the tail zero) when no
+  term asks for history or delay."""
+
+  GROUPS = ("policy", "critic")
+
+  @classmethod
+  def build(cls, d, env, pol, cri):
+    terms = (pol, cri)
+    if not any(c.history_length > 0 or c.delay_max_lag > 0 for g in terms for _, c in g):
+      return None
+    return cls(d, env, terms)
+
+  def __init__(self, d, env, terms):
+    om, n, dev = env.observation_manager, env.num_envs, torch.device(env.device)
+    self.om, self.n = om, n
+    self.segs = ([], [])  # per group: (term name, width, history, row offset)
+    self.rings = {}       # (group index, term index) -> ring tensor [n, max_lag + 1, w]
+    self.widths = [0, 0]
+    for g, gname in enumerate(self.GROUPS):
+      _need(om._group_obs_concatenate[gname], f"unconcatenated observation terms ({gname})")
+      _need(len(terms[g]) <= MAX_OBS_TERMS, "too many observation terms")
+      G = d.obs.group[g]
+      G.nterm = len(terms[g])
+      off = 0
+      for s, (name, c) in enumerate(terms[g]):
+        H = int(c.history_length)
+        _need(H <= MAX_HISTORY, f"observation history of {gname}/{name} past {MAX_HISTORY}")
+        _need(H == 0 or c.flatten_history_dim, f"unflattened observation history ({gname}/{name})")
+        w = int(math.prod(om._group_obs_term_dim[gname][s])) // max(H, 1)
+        G.seg[s].width, G.seg[s].history = w, H
+        if c.delay_max_lag > 0:
+          _need(c.delay_update_period == 0 and c.delay_hold_prob == 0.0 and c.delay_per_env,
+                f"observation delay policy of {gname}/{name}: update_period / hold_prob / "
+                "shared lag run on the torch managers")
+          _need(c.delay_max_lag <= MAX_LAG, f"observation delay of {gname}/{name} past {MAX_LAG}")
+          G.seg[s].min_lag, G.seg[s].max_lag = int(c.delay_min_lag), int(c.delay_max_lag)
+          ring = torch.zeros(n, c.delay_max_lag + 1, w, device=dev)
+          self.rings[(g, s)] = ring
+          G.delay_ring[s] = _ptr(ring)
+        self.segs[g].append((name, w, H, off))
+        off += w * max(H, 1)
+      self.widths[g] = off
+    self.fresh = torch.zeros(n, dtype=torch.uint8, device=dev)
+    self.delay_pushes = torch.zeros(n, dtype=torch.int32, device=dev)
+    self.delay_lag = torch.zeros(2 * MAX_OBS_TERMS, n, dtype=torch.int32, device=dev)
+    d.obs.fresh = _ptr(self.fresh, _U8)
+    d.obs.delay_pushes = _ptr(self.delay_pushes, _I32)
+    d.obs.delay_lag = _ptr(self.delay_lag, _I32)
+
+  def lags(self, group: str, term: str) -> torch.Tensor:
+    """The lag the last observe used for a delayed term, `[num_envs]` int32."""
+    g = self.GROUPS.index(group)
+    s = [nm for nm, *_ in self.segs[g]].index(term)
+    return self.delay_lag[g * MAX_OBS_TERMS + s]
+
+  def ring(self, group: str, term: str) -> torch.Tensor:
+    g = self.GROUPS.index(group)
+    return self.rings[(g, [nm for nm, *_ in self.segs[g]].index(term))]
+
+  def seed(self, obs: dict) -> None:
+    """The manager has appended at least once when the fused step is built (env.reset()
+    computes observations): continue from its buffers instead of backfilling.  The cached
+    group tensors already have the fused rows' layout."""
+    om = self.om
+    cached = om._obs_buffer if om._obs_buffer is not None else om.compute()
+    for gname in self.GROUPS:
+      obs[gname].copy_(cached[gname])
+    for g, gname in enumerate(self.GROUPS):
+      for s, (name, w, H, off) in enumerate(self.segs[g]):
+        h = om._group_obs_term_history_buffer[gname].get(name)
+        if h is not None:  # all history buffers of an env are pushed and reset together
+          self.fresh.copy_(h.num_pushes == 0)
+        db = om._group_obs_term_delay_buffer[gname].get(name)
+        if db is not None:
+          self.rings[(g, s)].copy_(db._buffer.buffer.reshape(self.n, -1, w))
+          self.delay_pushes.copy_(db._buffer.num_pushes.clamp(max=1 << 20))
+          self.delay_lag[g * MAX_OBS_TERMS + s].copy_(db.current_lags)
+
+  def hand_back(self, obs: dict) -> None:
+    """The reverse of `seed`, when the env returns to the torch managers."""
+    om = self.om
+    fresh = self.fresh.bool()
+    for g, gname in enumerate(self.GROUPS):
+      for s, (name, w, H, off) in enumerate(self.segs[g]):
+        h = om._group_obs_term_history_buffer[gname].get(name)
+        if h is not None and h.is_initialized:
+          h.buffer.copy_(obs[gname][:, off:off + H * w].reshape(h.buffer.shape))
+          h.num_pushes.copy_(torch.where(fresh, 0, h.num_pushes.clamp(min=1)))
+        db = om._group_obs_term_delay_buffer[gname].get(name)
+        if db is not None and db.is_initialized:
+          db._buffer.buffer.copy_(self.rings[(g, s)].reshape(db._buffer.buffer.shape))
+          db._buffer.num_pushes.copy_(self.delay_pushes)
+          db.current_lags.copy_(self.delay_lag[g * MAX_OBS_TERMS + s])
+    om._obs_buffer = {k: v.clone() for k, v in obs.items()}
 
 
 class FusedVelocityStep:
@@ -277,6 +403,7 @@ class FusedVelocityStep:
       _need(pol[i][1].noise is None, "noise on actions/command")
     d.npolicy = 9 + 3 * nj + 3
     d.ncritic = d.npolicy + (6 * d.nfeet if d.critic_extras else 0)
+    self._obs_history(d, env, pol, cri)
     self._io(d, env)
     return d
 
@@ -478,6 +605,13 @@ class FusedVelocityStep:
     d.noise_lin_vel, d.noise_ang_vel, d.noise_gravity = (_noise(pol[i][1]) for i in range(3))
     d.noise_joint_pos, d.noise_joint_vel = _noise(pol[3][1]), _noise(pol[4][1])
 
+  def _obs_history(self, d, env, pol, cri):
+    """Observation history / delay: the descriptor's segment tables and the row widths they
+    imply (the single-frame widths stay when no term asks for either)."""
+    self._obs_hist = FusedObsHistory.build(d, env, pol, cri)
+    if self._obs_hist is not None:
+      d.npolicy, d.ncritic = self._obs_hist.widths
+
   def _io(self, d, env):
     """Observation buffers, action pointers, seed, log scalars."""
     om, am, n, dev = env.observation_manager, env.action_manager, env.num_envs, torch.device(env.device)
@@ -487,6 +621,8 @@ class FusedVelocityStep:
     self.obs = {"policy": torch.zeros(n, d.npolicy, device=dev),
                 "critic": torch.zeros(n, d.ncritic, device=dev)}
     d.obs_policy, d.obs_critic = _ptr(self.obs["policy"]), _ptr(self.obs["critic"])
+    if self._obs_hist is not None:
+      self._obs_hist.seed(self.obs)
     d.action, d.prev_action = _ptr(am._action), _ptr(am._prev_action)
     d.prev_prev_action, d.joint_pos_target = _ptr(am._prev_prev_action), _ptr(rdata.joint_pos_target)
     d.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -553,6 +689,10 @@ class FusedVelocityStep:
     stops updating them (n = 0).  Called when the env drops or replaces this fused step
     (enable_graph); without it a later torch-manager step would advance air time twice per
     substep."""
+    if getattr(self, "_obs_hist", None) is not None:
+      # the observation history / delay state goes back to the manager's buffers
+      self._obs_hist.hand_back(self.obs)
+      self._obs_hist = None
     if not getattr(self, "_engine_air", False):
       return
     sim = self.env.sim
@@ -578,6 +718,9 @@ class FusedVelocityStep:
     self._task = h
 
   def __del__(self):
+    # no hand-back from a finaliser: it may run while the interpreter tears the manager's
+    # tensors down (enable_graph releases explicitly)
+    self._obs_hist = None
     try:
       self.release()
     except Exception:
@@ -771,6 +914,7 @@ class FusedJumpStep(FusedVelocityStep):
       _need(pol[i][1].noise is None, "noise beyond the proprioceptive terms")
     d.npolicy = 9 + 3 * nj + 2 + 2 * d.nfeet + 1
     d.ncritic = d.npolicy + 4 * d.nfeet
+    self._obs_history(d, env, pol, cri)
     self._io(d, env)
     return d
 

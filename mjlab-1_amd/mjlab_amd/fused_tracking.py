@@ -24,7 +24,8 @@ import torch
 from . import mdp
 from . import tracking as trk
 from ._lib import MjxError, check, lib
-from .fused import MAXJ, MAXT, Unsupported, _f2, _f62, _FP, _I64, _need, _noise, _ptr, _range6, _U8, _U64
+from .fused import (MAXJ, MAXT, FusedObsHistory, ObsState, Unsupported, _f2, _f62, _FP, _I64, _need,
+                    _noise, _ptr, _range6, _U8, _U64)
 
 MAXB, NMETRIC = 32, 13
 _I32 = ctypes.c_int
@@ -82,6 +83,7 @@ class TrackDesc(ctypes.Structure):
     ("obs_policy", _FP), ("obs_critic", _FP),
     ("log_reward", _FP), ("log_termination", _FP), ("log_metric", _FP),
     ("step_counter", _U64),
+    ("obs", ObsState),
   ]
 
 
@@ -358,11 +360,17 @@ class FusedTrackingStep:
       _need(polf[key].noise is None, "noise on command/actions")
     d.ncritic = 5 * nj + 9 * nmb + 15
     d.npolicy = 5 * nj + 9 + 3 * d.policy_anchor_pos + 3 * d.policy_lin_vel
+    # observation history / delay: segment tables and the row widths they imply
+    self._obs_hist = FusedObsHistory.build(d, env, pol, cri)
+    if self._obs_hist is not None:
+      d.npolicy, d.ncritic = self._obs_hist.widths
     _need(om.group_obs_dim["policy"] == (d.npolicy,) and om.group_obs_dim["critic"] == (d.ncritic,),
           "observation dims")
     self.obs = {"policy": torch.zeros(n, d.npolicy, device=dev),
                 "critic": torch.zeros(n, d.ncritic, device=dev)}
     d.obs_policy, d.obs_critic = _ptr(self.obs["policy"]), _ptr(self.obs["critic"])
+    if self._obs_hist is not None:
+      self._obs_hist.seed(self.obs)
     d.action, d.prev_action = _ptr(am._action), _ptr(am._prev_action)
     d.prev_prev_action, d.joint_pos_target = _ptr(am._prev_prev_action), _ptr(rdata.joint_pos_target)
     d.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -397,6 +405,13 @@ class FusedTrackingStep:
     if rc != 0:
       raise MjxError(self._L.mjx_track_last_error().decode())
     self._task = h
+
+  def release(self) -> None:
+    """Called when the env drops or replaces this fused step (enable_graph): the observation
+    history / delay state goes back to the manager's buffers."""
+    if getattr(self, "_obs_hist", None) is not None:
+      self._obs_hist.hand_back(self.obs)
+      self._obs_hist = None
 
   def __del__(self):
     try:

@@ -17,6 +17,8 @@ from typing import Any, Callable, Literal, Sequence
 
 import torch
 
+from .buffers import CircularBuffer, DelayBuffer
+
 # --------------------------------------------------------------------------- configs
 
 
@@ -64,6 +66,10 @@ class ObservationTermCfg(ManagerTermBaseCfg):
   scale: Any = None
   delay_min_lag: int = 0
   delay_max_lag: int = 0
+  delay_per_env: bool = True
+  delay_hold_prob: float = 0.0
+  delay_update_period: int = 0
+  delay_per_env_phase: bool = True
   history_length: int = 0
   flatten_history_dim: bool = True
 
@@ -337,15 +343,19 @@ class ActionManager(ManagerBase):
 
 # --------------------------------------------------------------------------- observations
 class ObservationManager(ManagerBase):
-  """`managers/observation_manager.py:154-208`: per term func -> clone -> noise (if the
-  group enables corruption) -> clip -> scale; groups concatenated on the last dim."""
+  """`managers/observation_manager.py:154-307`: per term func -> clone -> noise (if the
+  group enables corruption) -> clip -> scale -> delay -> history; groups concatenated on
+  the last dim, term-major (a term with history H owns H consecutive frames, oldest first)."""
 
   def _prepare_terms(self):
     self._group_obs_term_names: dict[str, list[str]] = {}
     self._group_obs_term_cfgs: dict[str, list[ObservationTermCfg]] = {}
     self._group_obs_term_dim: dict[str, list[tuple]] = {}
     self._group_obs_concatenate: dict[str, bool] = {}
+    self._group_obs_concatenate_dim: dict[str, int] = {}
     self._group_obs_dim: dict = {}
+    self._group_obs_term_delay_buffer: dict[str, dict[str, DelayBuffer]] = {}
+    self._group_obs_term_history_buffer: dict[str, dict[str, CircularBuffer]] = {}
     self._obs_buffer = None
     for gname, gcfg in self.cfg.items():
       if gcfg is None:
@@ -354,10 +364,11 @@ class ObservationManager(ManagerBase):
       for tname, tcfg in gcfg.terms.items():
         if tcfg is None:
           continue
-        if tcfg.history_length or tcfg.delay_max_lag:
-          raise NotImplementedError("observation history/delay buffers are out of scope")
         if not gcfg.enable_corruption:
           tcfg.noise = None
+        if gcfg.history_length is not None:  # the group's setting overrides every term's
+          tcfg.history_length = gcfg.history_length
+          tcfg.flatten_history_dim = gcfg.flatten_history_dim
         if tcfg.scale is not None and not isinstance(tcfg.scale, torch.Tensor):
           tcfg.scale = torch.tensor(tcfg.scale, dtype=torch.float32, device=self.device)
         self._resolve_common_term_cfg(tname, tcfg)
@@ -366,11 +377,36 @@ class ObservationManager(ManagerBase):
       self._group_obs_term_names[gname] = names
       self._group_obs_term_cfgs[gname] = cfgs
       self._group_obs_concatenate[gname] = gcfg.concatenate_terms
+      cd = gcfg.concatenate_dim
+      self._group_obs_concatenate_dim[gname] = cd + 1 if cd >= 0 else cd
+    n = self.num_envs
     for gname, cfgs in self._group_obs_term_cfgs.items():
-      dims = [tuple(c.func(self._env, **c.params).shape[1:]) for c in cfgs]
+      dims, delays, hists = [], {}, {}
+      for tname, c in zip(self._group_obs_term_names[gname], cfgs):
+        dim = tuple(c.func(self._env, **c.params).shape[1:])
+        if c.delay_max_lag > 0:
+          delays[tname] = DelayBuffer(
+            min_lag=c.delay_min_lag, max_lag=c.delay_max_lag, batch_size=n, device=self.device,
+            per_env=c.delay_per_env, hold_prob=c.delay_hold_prob,
+            update_period=c.delay_update_period, per_env_phase=c.delay_per_env_phase)
+        if c.history_length > 0:
+          hists[tname] = CircularBuffer(max_len=c.history_length, batch_size=n, device=self.device)
+          dim = (c.history_length, *dim)  # the history axis follows the batch axis
+          if c.flatten_history_dim:
+            dim = (int(math.prod(dim)),)
+        dims.append(dim)
       self._group_obs_term_dim[gname] = dims
+      self._group_obs_term_delay_buffer[gname] = delays
+      self._group_obs_term_history_buffer[gname] = hists
       if self._group_obs_concatenate[gname]:
-        self._group_obs_dim[gname] = (sum(int(math.prod(d)) for d in dims),)
+        if not hists or all(c.flatten_history_dim for c in cfgs):
+          self._group_obs_dim[gname] = (sum(int(math.prod(d)) for d in dims),)
+        else:  # unflattened history: equal-rank terms joined along concatenate_dim
+          ax = self._group_obs_concatenate_dim[gname]
+          ax = ax - 1 if ax > 0 else ax
+          tot = list(dims[0])
+          tot[ax] = sum(d[ax] for d in dims)
+          self._group_obs_dim[gname] = tuple(tot)
       else:
         self._group_obs_dim[gname] = dims
 
@@ -393,21 +429,49 @@ class ObservationManager(ManagerBase):
   def get_term_cfg(self, group_name: str, term_name: str):
     return self._group_obs_term_cfgs[group_name][self._group_obs_term_names[group_name].index(term_name)]
 
+  def _buffers(self):
+    for g in self._group_obs_term_names:
+      yield from self._group_obs_term_delay_buffer[g].values()
+      yield from self._group_obs_term_history_buffer[g].values()
+
+  @property
+  def has_buffers(self) -> bool:
+    return next(self._buffers(), None) is not None
+
   def reset(self, env_ids=None) -> dict:
     self._obs_buffer = None
     for cfgs in self._group_obs_term_cfgs.values():
       for c in _class_terms(cfgs):
         c.func.reset(env_ids=env_ids)
+    batch_ids = None if isinstance(env_ids, slice) else env_ids
+    for buf in self._buffers():
+      buf.reset(batch_ids=batch_ids)
+    return {}
+
+  def reset_masked(self, mask: torch.Tensor) -> dict:
+    """`reset(mask.nonzero())` as mask operations: no index list, no host sync, so the
+    sync-free env step stays capturable with history / delay buffers."""
+    self._obs_buffer = None
+    for cfgs in self._group_obs_term_cfgs.values():
+      for c in _class_terms(cfgs):
+        if hasattr(c.func, "reset_masked"):
+          c.func.reset_masked(mask)
+        else:
+          c.func.reset(env_ids=None)
+    for buf in self._buffers():
+      buf.reset_masked(mask)
     return {}
 
   def compute(self, update_history: bool = False):
     if not update_history and self._obs_buffer is not None:
       return self._obs_buffer
-    self._obs_buffer = {g: self.compute_group(g) for g in self._group_obs_term_names}
+    self._obs_buffer = {g: self.compute_group(g, update_history) for g in self._group_obs_term_names}
     return self._obs_buffer
 
   def compute_group(self, group_name: str, update_history: bool = False):
     out = {}
+    delays = self._group_obs_term_delay_buffer[group_name]
+    hists = self._group_obs_term_history_buffer[group_name]
     for name, c in zip(self._group_obs_term_names[group_name], self._group_obs_term_cfgs[group_name]):
       obs = c.func(self._env, **c.params).clone()
       if c.noise is not None:
@@ -416,9 +480,22 @@ class ObservationManager(ManagerBase):
         obs = obs.clip_(min=c.clip[0], max=c.clip[1])
       if c.scale is not None:
         obs = obs.mul_(c.scale)
+      if name in delays:
+        delays[name].append(obs)
+        obs = delays[name].compute()
+      if name in hists:
+        h = hists[name]
+        if update_history or not h.is_initialized:
+          h.append(obs)
+        # a copy: the buffer is shifted in place by the next append
+        obs = h.buffer.clone()
+        if c.flatten_history_dim:
+          obs = obs.reshape(self.num_envs, -1)
       out[name] = obs
     if self._group_obs_concatenate[group_name]:
-      return torch.cat([o.reshape(o.shape[0], -1) for o in out.values()], dim=-1)
+      if not hists or all(c.flatten_history_dim for c in self._group_obs_term_cfgs[group_name]):
+        return torch.cat([o.reshape(o.shape[0], -1) for o in out.values()], dim=-1)
+      return torch.cat(list(out.values()), dim=self._group_obs_concatenate_dim[group_name])
     return out
 
 
