@@ -214,6 +214,16 @@ int mjx_spec_register(const char* path);
  * rocprofv3 kernel trace or --pmc pass of the same command can attribute exactly the
  * timed steps' dispatches.  No reference counterpart. */
 int mjx_marker(int tag, void* stream);
+/* Diagnostics (host side only): how many kernel launches of each kind this process has issued
+ * through mjx_step / mjx_forward / mjx_forward_masked since it started or since the last
+ * mjx_launch_counts_reset.  out[0..12] count the step-kernel entry points by phase code
+ * (csrc/engine_impl.h phase_kernel), out[13] the Newton work-list kernel (classify); entries
+ * past 13 are zeroed.  A launch captured into a graph counts once, at capture.  The tests use
+ * it to show that a launch variant (a batch-size threshold or MJX355_* knob of
+ * csrc/engine.hip launch_step) really ran.  Returns 0, or -1 for a null `out` or n < 0.  No
+ * reference counterpart. */
+int mjx_launch_counts(int64_t* out, int n);
+int mjx_launch_counts_reset(void);
 
 #ifdef __cplusplus
 }

@@ -1003,6 +1003,19 @@ int mjx_sim_info(const mjxSim* s, int32_t* out) {
   return 0;
 }
 
+int mjx_launch_counts(int64_t* out, int n) {
+  if (!out || n < 0) return fail("mjx_launch_counts: null output or negative length");
+  std::vector<long long> v(n);
+  mjx::launch_counts(v.data(), n);
+  for (int i = 0; i < n; i++) out[i] = (int64_t)v[i];
+  return 0;
+}
+
+int mjx_launch_counts_reset(void) {
+  mjx::launch_counts_reset();
+  return 0;
+}
+
 int mjx_marker(int tag, void* stream) {
   hipError_t e = mjx::launch_marker(tag, (hipStream_t)stream);
   if (e != hipSuccess) return fail(std::string("marker launch: ") + hipGetErrorString(e));

@@ -197,4 +197,29 @@ constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false) {
   return L;
 }
 
+// What the J-in-global Newton kernels assume of their carve LJ = make_lds(d, 1, true): they
+// fill it from the B pack, which phase A lays out by the full carve LB = make_lds(d, 1), with
+// cp_pack(S + LJ.qacc_smooth, pack + LB.qacc_smooth, LB.efc_J - LB.qacc_smooth).  So every pack
+// region up to efc_J sits at LB's offset, and the copy ends where LJ's pack ends (efc_J holds
+// no rows there), before the first region outside the pack.
+constexpr bool jg_carve_agrees(const Dims& d) {
+  const Lds b = make_lds(d, 1), j = make_lds(d, 1, true);
+  return j.ints == b.ints && j.M == b.M && j.qacc_smooth == b.qacc_smooth &&
+         j.qfrc_smooth == b.qfrc_smooth && j.efc_aref == b.efc_aref && j.efc_D == b.efc_D &&
+         j.efc_J == b.efc_J && j.pack_len == b.efc_J && j.pack_len <= j.total;
+}
+// ... checked at compile time for every compiled specialisation (the generic kernels' carves:
+// tests/test_carve_invariants.py)
+#ifdef MJX_SPECS_FILE
+#define MJX_CARVE_SPECS_FILE MJX_SPECS_FILE
+#else
+#define MJX_CARVE_SPECS_FILE "specs.inc"
+#endif
+#define MJX_SPEC(id, scene, ...)                           \
+  static_assert(jg_carve_agrees(Dims{__VA_ARGS__}),        \
+                "spec " #id ": the J-in-global carve moves a B-pack offset before efc_J");
+#include MJX_CARVE_SPECS_FILE
+#undef MJX_SPEC
+#undef MJX_CARVE_SPECS_FILE
+
 }  // namespace mjx

@@ -276,5 +276,11 @@ int choose_row_classes(const Dims& d, int spec, int (&caps)[kRowClasses]);
 hipError_t launch_reset(const Dims& d, const DModel& m, const DData& dd, const uint8_t* mask,
                         int nworld, int con_stride, hipStream_t stream);
 hipError_t launch_marker(int tag, hipStream_t stream);  // empty kernel (profiling brackets)
+// Launch counters (host side): launches issued by this process per phase code of phase_kernel
+// (0 .. 12) and of the classify kernel (kLaunchClassify); mjx_launch_counts.
+constexpr int kLaunchClassify = 13;
+constexpr int kLaunchCounters = 14;
+void launch_counts(long long* out, int n);
+void launch_counts_reset();
 
 }  // namespace mjx

@@ -4,6 +4,7 @@
 // in engine_impl.h; spec.hip compiles them once per specs.inc entry.
 #include "engine_impl.h"
 
+#include <atomic>
 #include <vector>
 
 namespace mjx {
@@ -184,6 +185,30 @@ static StepFn step_fn(const Params& host, int ph) {
   StepFn f = host.spec > 0 ? spec_fn(host.spec, ph) : nullptr;
   return f ? f : generic_fn(host.d.nv, ph);
 }
+// Launch counters (host side only; mjx_launch_counts): how many launches of each phase code
+// of phase_kernel, and of classify_kernel (kLaunchClassify), this process has issued.  Counted
+// where a launch is issued, not where step_fn looks a kernel up (look-ups also happen for
+// kernels that are never launched), so a test of a launch variant can tell that its variant
+// ran.  A captured graph's launches count once, at capture.
+static std::atomic<long long> g_launches[kLaunchCounters];
+void launch_counts(long long* out, int n) {
+  for (int i = 0; i < n; i++)
+    out[i] = i < kLaunchCounters ? g_launches[i].load(std::memory_order_relaxed) : 0;
+}
+void launch_counts_reset() {
+  for (auto& c : g_launches) c.store(0, std::memory_order_relaxed);
+}
+// hipLaunchKernelGGL of the one-wave kernel `f`, counted under phase code `code`
+#define MJX_LAUNCH(code, f, grid, lds, st, ...)                              \
+  do {                                                                       \
+    g_launches[code].fetch_add(1, std::memory_order_relaxed);                \
+    hipLaunchKernelGGL(f, grid, dim3(kWave), lds, st, __VA_ARGS__);          \
+  } while (0)
+#define MJX_LAUNCH_CLASSIFY(st, ...)                                                       \
+  do {                                                                                     \
+    g_launches[kLaunchClassify].fetch_add(1, std::memory_order_relaxed);                   \
+    hipLaunchKernelGGL(classify_kernel, dim3(1), dim3(kClassifyThreads), 0, st, __VA_ARGS__); \
+  } while (0)
 // The full-capacity Newton class and the masked forward run the latency kernel
 // (step_newton_lat); MJX355_NEWTON_LAT=0 keeps them on step_phase<NR, 1> (A/B diagnostic).
 static bool newton_lat() {
@@ -305,9 +330,16 @@ static bool chain_env(int cls, int nworld) {
 hipError_t prepare_step(const Params& host) {
   size_t shmem[3] = {lds_bytes(host, 0), lds_bytes(host, 1), lds_bytes(host, 2)};
   for (int k = 0; k < host.nrowclass; k++) shmem[1] = std::max(shmem[1], lds_bytes(host, 3 + k));
-  for (int ph = 0; ph < 9; ph++) {  // phase codes of phase_kernel
-    const size_t need = ph >= 5 ? std::max(shmem[0], std::max(shmem[1], shmem[2]))
-                                : shmem[ph == 3 ? 1 : ph == 4 ? 0 : ph];
+  // Codes 9 and 10 run in the J-in-global carve, which never passes the 64 KiB default (15,904
+  // B at nv 64 and 256 rows, the largest the engine admits: tests/carve_invariants.cpp).  Code
+  // 11's chain also holds phases C and A, whose carve grows with the geoms that keep an LDS
+  // frame (152,176 B found among admitted models), and code 12 the full fast carve (54,944 B
+  // at its default of at most 160 rows, 81,440 B at 256 rows when MJX355_HEAVY_CAP forces it).
+  for (int ph = 0; ph < 13; ph++) {  // phase codes of phase_kernel
+    const size_t need = ph == 9 || ph == 10 ? lds_bytes(host, kLdsJG)
+                        : ph == 12          ? shmem[1]
+                        : ph >= 5           ? std::max(shmem[0], std::max(shmem[1], shmem[2]))
+                                            : shmem[ph == 3 ? 1 : ph == 4 ? 0 : ph];
     const StepFn f = step_fn(host, ph);
     if (need > 64 * 1024 && f) {
       hipError_t e = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -332,6 +364,7 @@ static hipError_t launch_split_classes(const Params& host, const Params* dev, in
                                        const SideStream* side, int nsplit, bool piped) {
   const StepFn fA = step_fn(host, 0), fB = step_fn(host, 1), fC = step_fn(host, 2);
   const StepFn fBL = newton_lat() ? step_fn(host, 3) : fB;
+  const int cBL = newton_lat() ? 3 : 1;  // fBL's phase code
   const int nc = host.nrowclass;
   hipStream_t sst[kMaxSplit];
   int wb[kMaxSplit + 1];
@@ -366,9 +399,9 @@ static hipError_t launch_split_classes(const Params& host, const Params* dev, in
       const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
       if (n <= 0) continue;
       if (!piped || sub == 0)
-        hipLaunchKernelGGL(fA, dim3(n), dim3(kWave), lds_bytes(host, 0), sst[k], dev, w0, w1, k,
-                           last, integrate, nullptr);
-      hipLaunchKernelGGL(classify_kernel, dim3(1), dim3(kClassifyThreads), 0, sst[k], dev, w0, w1,
+        MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), sst[k], dev, w0, w1, k, last, integrate,
+                   nullptr);
+      MJX_LAUNCH_CLASSIFY(sst[k], dev, w0, w1,
                          k, nullptr);
     }
     if (join_all(false) != hipSuccess || fork_all(true) != hipSuccess) return e;
@@ -376,14 +409,14 @@ static hipError_t launch_split_classes(const Params& host, const Params* dev, in
       const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
       if (n <= 0) continue;
       auto class_chain = [&](hipStream_t cs, int cls) {
-        hipLaunchKernelGGL(cls ? fB : fBL, dim3(n), dim3(kWave), lds_bytes(host, cls ? 2 + cls : 1), cs, dev,
-                           w0, w1, k, last, cls, nullptr);
+        MJX_LAUNCH(cls ? 1 : cBL, cls ? fB : fBL, dim3(n), lds_bytes(host, cls ? 2 + cls : 1), cs, dev,
+                   w0, w1, k, last, cls, nullptr);
         if (!piped) return;
-        hipLaunchKernelGGL(fC, dim3(n), dim3(kWave), lds_bytes(host, 2), cs, dev, w0, w1,
-                           k | (cls + 1) << 8, last, integrate, nullptr);
+        MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), cs, dev, w0, w1, k | (cls + 1) << 8, last,
+                   integrate, nullptr);
         if (!last)
-          hipLaunchKernelGGL(fA, dim3(n), dim3(kWave), lds_bytes(host, 0), cs, dev, w0, w1,
-                             k | (cls + 1) << 8, sub + 1 == nsubstep - 1, integrate, nullptr);
+          MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), cs, dev, w0, w1, k | (cls + 1) << 8,
+                     sub + 1 == nsubstep - 1, integrate, nullptr);
       };
       for (int c = 0; c < nc; c++) class_chain(side->stream[k][c], c == 0 ? 0 : nc + 1 - c);
       class_chain(sst[k], 1);
@@ -394,8 +427,8 @@ static hipError_t launch_split_classes(const Params& host, const Params* dev, in
     for (int k = 0; k < nsplit; k++) {
       const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
       if (n > 0)
-        hipLaunchKernelGGL(fC, dim3(n), dim3(kWave), lds_bytes(host, 2), sst[k], dev, w0, w1, k,
-                           last, integrate, nullptr);
+        MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), sst[k], dev, w0, w1, k, last, integrate,
+                   nullptr);
     }
     if (join_all(false) != hipSuccess) return e;
   }
@@ -424,12 +457,12 @@ static void ovf_chain(const Params& host, const Params* dev, const Params& hbig,
   const int g = std::min(hbig.ovf_cap, grid_env > 0 ? grid_env : in_line ? kOvfGridInline : kOvfGrid);
   const int sel = k | kSelOvf | (par ? kSelRPar : 0);
   const bool next = next_a && !last;
-  hipLaunchKernelGGL(step_fn(hbig, 5), dim3(g), dim3(kWave), lds_resolve(hbig), cs, dbig, w0, w1,
-                     sel | (next ? 0 : kSelClr), last, integrate, nullptr);
+  MJX_LAUNCH(5, step_fn(hbig, 5), dim3(g), lds_resolve(hbig), cs, dbig, w0, w1,
+             sel | (next ? 0 : kSelClr), last, integrate, nullptr);
   if (next)
-    hipLaunchKernelGGL(step_fn(host, 4), dim3(g), dim3(kWave), lds_bytes(host, 0), cs, dev, w0, w1,
-                       sel | kSelClr | ((sub + 1) & 1 ? kSelAPar : 0), sub + 1 == nsubstep - 1,
-                       integrate, nullptr);
+    MJX_LAUNCH(4, step_fn(host, 4), dim3(g), lds_bytes(host, 0), cs, dev, w0, w1,
+               sel | kSelClr | ((sub + 1) & 1 ? kSelAPar : 0), sub + 1 == nsubstep - 1, integrate,
+               nullptr);
 }
 
 static bool ovf_stream_env() {
@@ -486,21 +519,21 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
       return !e || atoi(e) != 0;
     }();
     if (const StepFn fM = fused ? step_fn(*hbig, 8) : nullptr) {
-      hipLaunchKernelGGL(fM, dim3(nworld), dim3(kWave), lds_resolve(*hbig), stream, dbig, 0, nworld, 0,
-                         1, integrate, mask);
+      MJX_LAUNCH(8, fM, dim3(nworld), lds_resolve(*hbig), stream, dbig, 0, nworld, 0, 1, integrate,
+                 mask);
       return hipGetLastError();
     }
     const StepFn fA = step_fn(*hbig, 0), fBL = step_fn(*hbig, 3), fC = step_fn(*hbig, 2);
-    hipLaunchKernelGGL(fA, dim3(nworld), dim3(kWave), lds_bytes(*hbig, 0), stream, dbig, 0, nworld, 0,
-                       1, integrate, mask);
-    hipLaunchKernelGGL(fBL, dim3(nworld), dim3(kWave), lds_bytes(*hbig, 1), stream, dbig, 0, nworld, 0,
-                       1, -1, mask);
-    hipLaunchKernelGGL(fC, dim3(nworld), dim3(kWave), lds_bytes(*hbig, 2), stream, dbig, 0, nworld, 0,
-                       1, integrate, mask);
+    MJX_LAUNCH(0, fA, dim3(nworld), lds_bytes(*hbig, 0), stream, dbig, 0, nworld, 0, 1, integrate,
+               mask);
+    MJX_LAUNCH(3, fBL, dim3(nworld), lds_bytes(*hbig, 1), stream, dbig, 0, nworld, 0, 1, -1, mask);
+    MJX_LAUNCH(2, fC, dim3(nworld), lds_bytes(*hbig, 2), stream, dbig, 0, nworld, 0, 1, integrate,
+               mask);
     return hipGetLastError();
   }
   const StepFn fA = step_fn(host, 0), fB = step_fn(host, 1), fC = step_fn(host, 2);
   const StepFn fBL = newton_lat() ? step_fn(host, 3) : fB;
+  const int cBL = newton_lat() ? 3 : 1;  // fBL's phase code
   const int nc = host.nrowclass;
   if (nc > 0 && !side) return hipErrorInvalidValue;
   const bool ovf = hbig && side && host.ovf_resolve;
@@ -559,8 +592,8 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
       const bool piped = nc > 0 && !mask && pipe;
       const bool nexta = piped || fR;  // the next substep's phase A runs behind this one's C
       if (!nexta || sub == 0)
-        hipLaunchKernelGGL(fA, dim3(n), dim3(kWave), lds_bytes(host, 0), st, dev, w0, w1, k | apar,
-                           last, integrate, mask);
+        MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), st, dev, w0, w1, k | apar, last, integrate,
+                   mask);
       // the re-solve chain: forked after this substep's phase A (and classify), joined at the
       // end of the substep -- the empty chain overlaps the class launches
       // split batches: in line behind phase C on the split stream (a fork from a split
@@ -611,12 +644,12 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
           return !e || atoi(e) != 0;
         }();
         const StepFn fMJ = masked_jg && newton_lat() ? step_fn(host, 9) : nullptr;
-        hipLaunchKernelGGL(fMJ ? fMJ : fBL, dim3(n), dim3(kWave), lds_bytes(host, fMJ ? kLdsJG : 1), st,
-                           dev, w0, w1, k, last, -1, mask);
+        MJX_LAUNCH(fMJ ? 9 : cBL, fMJ ? fMJ : fBL, dim3(n), lds_bytes(host, fMJ ? kLdsJG : 1), st,
+                   dev, w0, w1, k, last, -1, mask);
         // (MJX355_MASKED_BIG=0) masked worlds past the fast carve: re-solved in line
         if (ovf) ovf_chain(host, dev, *hbig, dbig, st, k, w0, w1, sub, nsubstep, integrate, false, true);
       } else if (nc > 0) {
-        hipLaunchKernelGGL(classify_kernel, dim3(1), dim3(kClassifyThreads), 0, st, dev, w0, w1,
+        MJX_LAUNCH_CLASSIFY(st, dev, w0, w1,
                            k, mask);
         // MJX355_OVF_STREAM=1 (diagnostic, scripts/capture_probe*): the re-solve chain on a
         // stream of its own, forked here and joined after the class joins -- round 4's
@@ -633,31 +666,31 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
         // as one launch (step_chain) unless MJX355_CHAIN=0
         auto class_chain = [&](hipStream_t cs, int cls) {
           const bool cjg = cls == 0 && newton_lat() && jg_mode(nworld) == 1;
-          const StepFn fX = piped && chain_env(cls, nworld)
-                                ? step_fn(host, cls == 0 && newton_lat() ? (cjg ? 11 : 7) : 6)
-                                : nullptr;
+          const int cX = cls == 0 && newton_lat() ? (cjg ? 11 : 7) : 6;
+          const StepFn fX = piped && chain_env(cls, nworld) ? step_fn(host, cX) : nullptr;
           if (fX) {
             const int selx = k | (cls + 1) << 8 | (last ? 0 : kSelChainA) |
                              (((sub + 1) & 1) ? kSelAPar : 0) |
                              (sub + 1 == nsubstep - 1 ? kSelNextLast : 0);
-            hipLaunchKernelGGL(fX, dim3(n), dim3(kWave), lds_chain(host, cls, !last, cjg), cs, dev,
-                               w0, w1, selx, last, integrate, mask);
+            MJX_LAUNCH(cX, fX, dim3(n), lds_chain(host, cls, !last, cjg), cs, dev, w0, w1, selx,
+                       last, integrate, mask);
             return;
           }
           const int jg = cls == 0 ? jg_mode(nworld) : 0;
           const StepFn fJ = jg == 1 && newton_lat() ? step_fn(host, 9) : jg == 2 ? step_fn(host, 10) : nullptr;
           const StepFn fBH = cls == 0 && !fJ && heavy_cap(host) && newton_lat() ? step_fn(host, 12) : fBL;
           const int pr = fBH != fBL ? kSelPrio : 0;
-          hipLaunchKernelGGL(cls ? fB : fJ ? fJ : fBH, dim3(n), dim3(kWave),
-                             lds_bytes(host, cls ? 2 + cls : fJ ? kLdsJG : 1), cs, dev, w0, w1, k | pr, last,
-                             cls, mask);
+          const int cB = cls ? 1 : fJ ? (jg == 2 ? 10 : 9) : fBH != fBL ? 12 : cBL;
+          MJX_LAUNCH(cB, cls ? fB : fJ ? fJ : fBH, dim3(n),
+                     lds_bytes(host, cls ? 2 + cls : fJ ? kLdsJG : 1), cs, dev, w0, w1, k | pr, last,
+                     cls, mask);
           if (!piped) return;
-          hipLaunchKernelGGL(fC, dim3(n), dim3(kWave), lds_bytes(host, 2), cs, dev, w0, w1,
-                             k | (cls + 1) << 8 | pr, last, integrate, mask);
+          MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), cs, dev, w0, w1, k | (cls + 1) << 8 | pr,
+                     last, integrate, mask);
           if (!last)
-            hipLaunchKernelGGL(fA, dim3(n), dim3(kWave), lds_bytes(host, 0), cs, dev, w0, w1,
-                               k | (cls + 1) << 8 | (((sub + 1) & 1) ? kSelAPar : 0) | pr,
-                               sub + 1 == nsubstep - 1, integrate, mask);
+            MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), cs, dev, w0, w1,
+                       k | (cls + 1) << 8 | (((sub + 1) & 1) ? kSelAPar : 0) | pr,
+                       sub + 1 == nsubstep - 1, integrate, mask);
         };
         for (int c = 0; c < nc; c++) {
           const int cls = c == 0 ? 0 : nc + 1 - c;  // 0, then nc, nc-1, ..., 2
@@ -686,8 +719,8 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
         if (!mfirst && (e = ovf_launch()) != hipSuccess) return e;
         const int selx = k | (last ? 0 : kSelChainA) | (((sub + 1) & 1) ? kSelAPar : 0) |
                          (sub + 1 == nsubstep - 1 ? kSelNextLast : 0);
-        hipLaunchKernelGGL(fR, dim3(n), dim3(kWave), lds_chain(host, 0, !last), st, dev, w0, w1, selx,
-                           last, integrate, mask);
+        MJX_LAUNCH(6, fR, dim3(n), lds_chain(host, 0, !last), st, dev, w0, w1, selx, last,
+                   integrate, mask);
         if (mfirst && (e = ovf_launch()) != hipSuccess) return e;
         if ((e = join_ovf()) != hipSuccess) return e;
         continue;
@@ -696,12 +729,11 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
         if (!mfirst && (e = ovf_launch()) != hipSuccess) return e;
         // (MJX355_NEWTON_JG=2 on a model without row classes: J from global memory as well)
         const StepFn fBJ = newton_jg() == 2 ? step_fn(host, 10) : nullptr;  // (A/B only)
-        hipLaunchKernelGGL(fBJ ? fBJ : fB, dim3(n), dim3(kWave), lds_bytes(host, fBJ ? kLdsJG : 1), st,
-                           dev, w0, w1, k, last, 0, mask);
+        MJX_LAUNCH(fBJ ? 10 : 1, fBJ ? fBJ : fB, dim3(n), lds_bytes(host, fBJ ? kLdsJG : 1), st, dev,
+                   w0, w1, k, last, 0, mask);
         if (mfirst && (e = ovf_launch()) != hipSuccess) return e;
       }
-      hipLaunchKernelGGL(fC, dim3(n), dim3(kWave), lds_bytes(host, 2), st, dev, w0, w1, k, last,
-                         integrate, mask);
+      MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), st, dev, w0, w1, k, last, integrate, mask);
       if (nc == 0 && (e = join_ovf()) != hipSuccess) return e;
     }
   }

@@ -33,6 +33,24 @@ def g1_states(model, n, seed=0, height_jitter=0.03, joint_jitter=0.15, vel_scale
   return q, qv, ctrl
 
 
+def hfield_states(m, n, seed, dz=(-0.04, 0.02)):
+  """Seeded G1 states on the spawn platforms of random patches of a heightfield terrain
+  (scene arrays["terrain_origins"]), the pelvis 0.55 m + dz above the patch origin."""
+  rng = np.random.default_rng(seed)
+  o = m.arrays["terrain_origins"]
+  q = np.tile(m.key_qpos, (n, 1))
+  for i in range(n):
+    r, c = rng.integers(0, o.shape[0]), rng.integers(0, o.shape[1])
+    q[i, :2] = o[r, c, :2] + rng.uniform(-0.6, 0.6, 2)  # on the spawn platform
+    q[i, 2] = o[r, c, 2] + 0.55 + rng.uniform(*dz)
+  q[:, 7:] += rng.uniform(-0.1, 0.1, (n, m.nq - 7))
+  qv = rng.normal(0, 0.3, (n, m.nv))
+  qv[:, :3] *= 0.3
+  jq = np.array([m.jnt_qposadr[j] for j in m.actuator_trnid])
+  ctrl = q[:, jq] + rng.uniform(-0.2, 0.2, (n, m.nu))
+  return q, qv, ctrl
+
+
 def oracle_step(model, q, qv, qws, ctrl, step=True, nconmax=64, njmax=160):
   outs = []
   for i in range(q.shape[0]):

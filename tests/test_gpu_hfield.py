@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity_util import oracle_step
+from parity_util import hfield_states as _states, oracle_step
 
 pytestmark = pytest.mark.gpu
 
@@ -24,22 +24,6 @@ def _sim(m, n, device):
   cfg = SimulationCfg(nconmax=48, njmax=160,
                       mujoco=MujocoCfg(timestep=m.timestep, iterations=10, ls_iterations=20))
   return Simulation(n, cfg, m, device)
-
-
-def _states(m, n, seed, dz=(-0.04, 0.02)):
-  rng = np.random.default_rng(seed)
-  o = m.arrays["terrain_origins"]
-  q = np.tile(m.key_qpos, (n, 1))
-  for i in range(n):
-    r, c = rng.integers(0, o.shape[0]), rng.integers(0, o.shape[1])
-    q[i, :2] = o[r, c, :2] + rng.uniform(-0.6, 0.6, 2)  # on the spawn platform
-    q[i, 2] = o[r, c, 2] + 0.55 + rng.uniform(*dz)
-  q[:, 7:] += rng.uniform(-0.1, 0.1, (n, m.nq - 7))
-  qv = rng.normal(0, 0.3, (n, m.nv))
-  qv[:, :3] *= 0.3
-  jq = np.array([m.jnt_qposadr[j] for j in m.actuator_trnid])
-  ctrl = q[:, jq] + rng.uniform(-0.2, 0.2, (n, m.nu))
-  return q, qv, ctrl
 
 
 def _load(sim, q, qv, ctrl):
