@@ -207,8 +207,10 @@ struct Params {
 // `sel` launch argument of the step kernels: bits 0-7 batch split, 8-15 row class + 1 (the
 // piped C / next-A launches of a class), kSelOvf: the world is the blockIdx-th entry of the
 // overflow list of parity kSelRPar, kSelAPar: the parity of the substep phase A computes
-// (the list it appends overflowing worlds to).
-// workgroups of a re-solve launch (each loops over listed worlds).  Measured (G1 4,096 at a
+// (the list it appends overflowing worlds to); the further bits are described where they are
+// defined below.
+
+// Workgroups of a re-solve launch (each loops over listed worlds).  Measured (G1 4,096 at a
 // 20-contact / 80-row fast carve, 3.5 % of world-substeps re-solved): 64 workgroups 1.43 M
 // env-steps/s, 256 1.69 M, 512 1.65 M; with nothing listed the grid size is not measurable.
 constexpr int kOvfGrid = 256;
@@ -236,7 +238,7 @@ constexpr int kSelClr = 1 << 19;  // the re-solve launch that empties its list o
 constexpr int kSelChainA = 1 << 20;
 constexpr int kSelNextLast = 1 << 21;
 constexpr int kSelFusedA = 1 << 22;
-// the full-capacity class's launches (engine.hip heavy_cap): its waves raise their issue
+// the full-capacity class's launches (launch_select.h heavy_cap): its waves raise their issue
 // priority (s_setprio) over the bulk-class waves sharing their SIMDs
 constexpr int kSelPrio = 1 << 23;
 
@@ -276,10 +278,37 @@ int choose_row_classes(const Dims& d, int spec, int (&caps)[kRowClasses]);
 hipError_t launch_reset(const Dims& d, const DModel& m, const DData& dd, const uint8_t* mask,
                         int nworld, int con_stride, hipStream_t stream);
 hipError_t launch_marker(int tag, hipStream_t stream);  // empty kernel (profiling brackets)
-// Launch counters (host side): launches issued by this process per phase code of phase_kernel
-// (0 .. 12) and of the classify kernel (kLaunchClassify); mjx_launch_counts.
-constexpr int kLaunchClassify = 13;
-constexpr int kLaunchCounters = 14;
+// Phase codes: which step kernel a launch runs (engine_impl.h phase_kernel).  The numbers are
+// public: they index the launch counters (mjx_launch_counts, include/mjx355.h).
+enum PhaseCode : int {
+  kPhA = 0,             // phase A (step_phase)
+  kPhB = 1,             // phase B, the throughput Newton kernel (step_phase); a row class's carve
+  kPhC = 2,             // phase C (step_phase)
+  kPhNewtonLat = 3,     // phase B, the latency Newton kernel (step_newton_lat)
+  kPhOvfNextA = 4,      // the re-solve chain's next phase A over its list, in the fast carve (step_ovf)
+  kPhResolve = 5,       // a listed world's whole substep at full capacity (step_resolve)
+  kPhChain = 6,         // a row class's (or range's) B -> C -> next A as one launch (step_chain)
+  kPhChainLat = 7,      // that chain with the latency Newton kernel (the full-capacity class)
+  kPhMasked = 8,        // the masked forward's A -> B -> C in the max carve (step_masked)
+  kPhNewtonLatJG = 9,   // latency Newton, J read from the B pack in global memory
+  kPhNewtonJG = 10,     // throughput Newton, J in global memory (step_phase_jg)
+  kPhChainLatJG = 11,   // the full-capacity class's latency chain, J in global memory
+  kPhNewtonLatCap = 12, // latency Newton at the throughput kernels' register budget (heavy_cap)
+  kPhaseCodes = 13
+};
+// LDS carve index of a launch's Newton part: Params::LP[carve], or Params::LPJ for kLdsJG
+// (engine_impl.h lds_of).
+enum Carve : int {
+  kCarveA = 0,
+  kCarveB = 1,       // phase B at full row capacity
+  kCarveC = 2,
+  kCarveClass0 = 3,  // + k: phase B of Newton row class k
+  kLdsJG = 9         // phase B at full capacity with J in global memory (make_lds jglobal)
+};
+// Launch counters (host side): launches issued by this process per phase code and of the
+// classify kernel (kLaunchClassify); mjx_launch_counts.
+constexpr int kLaunchClassify = kPhaseCodes;
+constexpr int kLaunchCounters = kPhaseCodes + 1;
 void launch_counts(long long* out, int n);
 void launch_counts_reset();
 

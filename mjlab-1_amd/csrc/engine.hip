@@ -3,6 +3,7 @@
 // (generic vs model-specialised, specs.inc) and the launchers.  The kernels themselves are
 // in engine_impl.h; spec.hip compiles them once per specs.inc entry.
 #include "engine_impl.h"
+#include "launch_select.h"
 
 #include <atomic>
 #include <vector>
@@ -181,12 +182,12 @@ static StepFn spec_fn(int spec, int ph) {
     default: return nullptr;
   }
 }
-static StepFn step_fn(const Params& host, int ph) {
+static StepFn step_fn(const Params& host, PhaseCode ph) {
   StepFn f = host.spec > 0 ? spec_fn(host.spec, ph) : nullptr;
   return f ? f : generic_fn(host.d.nv, ph);
 }
-// Launch counters (host side only; mjx_launch_counts): how many launches of each phase code
-// of phase_kernel, and of classify_kernel (kLaunchClassify), this process has issued.  Counted
+// Launch counters (host side only; mjx_launch_counts): how many launches of each PhaseCode,
+// and of classify_kernel (kLaunchClassify), this process has issued.  Counted
 // where a launch is issued, not where step_fn looks a kernel up (look-ups also happen for
 // kernels that are never launched), so a test of a launch variant can tell that its variant
 // ran.  A captured graph's launches count once, at capture.
@@ -209,39 +210,30 @@ void launch_counts_reset() {
     g_launches[kLaunchClassify].fetch_add(1, std::memory_order_relaxed);                   \
     hipLaunchKernelGGL(classify_kernel, dim3(1), dim3(kClassifyThreads), 0, st, __VA_ARGS__); \
   } while (0)
-// The full-capacity Newton class and the masked forward run the latency kernel
-// (step_newton_lat); MJX355_NEWTON_LAT=0 keeps them on step_phase<NR, 1> (A/B diagnostic).
-static bool newton_lat() {
-  static const bool on = [] {
-    const char* e = getenv("MJX355_NEWTON_LAT");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
+// The launch-time knobs (launch_select.h LaunchKnobs): read once, on first use, and cached for
+// the life of the process.
+static const LaunchKnobs& knobs() {
+  static const LaunchKnobs k = read_launch_knobs([](const char* name) { return getenv(name); });
+  return k;
 }
-// The full-capacity class's latency Newton kernel at the throughput kernels' 168 VGPRs (phase
-// code 12; naturally ~193, 68 B per lane spilled when capped), its waves at raised issue
-// priority (kSelPrio): a SIMD running a heavy world keeps two bulk-class waves beside it instead
-// of one, and the heavy wave still issues first.  Measured (three interleaved rounds on one
-// box): G1 velocity 4,096 +0.4 / +0.7 / +1.2 %, rough G1 +0.4 / +0.2 / +0.8 %; tracking (its
-// 56 / 200 carve, heavy worlds up to ~190 rows) -0.7 / -0.3 / -0.6 %: on for fast carves of at
-// most 160 rows.  MJX355_HEAVY_CAP=0/1 forces.
-static bool heavy_cap(const Params& host) {
-  static const int mode = [] {
-    const char* e = getenv("MJX355_HEAVY_CAP");
-    return e ? atoi(e) : -1;
-  }();
-  return mode >= 0 ? mode != 0 : host.d.njmax <= 160;
-}
-// The full-capacity row class (the heavy worlds of the fast carve) reads the constraint
-// Jacobian from the B pack in global memory (carve kLdsJG) instead of an LDS copy.
-// MJX355_NEWTON_JG (A/B): 0 off, 1 the latency kernel (phase code 9), 2 the throughput kernel
-// (phase code 10); with MJX355_CHAIN covering the full-capacity class, its chain (code 11).
-static int newton_jg() {
-  static const int mode = [] {
-    const char* e = getenv("MJX355_NEWTON_JG");
-    return e ? atoi(e) : -1;
-  }();
-  return mode;
+// The worlds [w0, w1) of batch split k as a launch set takes them: the Params whose kernels and
+// carves it uses (host copy for the launch geometry, device copy for the kernels) and the
+// step's mask.
+struct Worlds {
+  const Params& host;
+  const Params* dev;
+  int k, w0, w1;
+  const uint8_t* mask;
+};
+// One launch of phase code `code` for row class `cls` over W, a workgroup per world (or `grid`
+// workgroups), its dynamic LDS from lds_need.  `arg`: the kernels' sixth argument (integrate
+// for phases A and C and what holds them, the row class for a Newton launch).  step_fn never
+// returns null for a phase code: the generic kernels stand in for every role.
+static void launch(const Worlds& W, PhaseCode code, int cls, bool with_next_a, hipStream_t st,
+                   int sel, int last, int arg, int grid = -1) {
+  MJX_LAUNCH(code, step_fn(W.host, code), dim3(grid >= 0 ? grid : W.w1 - W.w0),
+             lds_need(W.host, knobs(), code, cls, with_next_a), st, W.dev, W.w0, W.w1, sel, last,
+             arg, W.mask);
 }
 
 int find_spec(const Dims& d, const int* dof_parentid) {
@@ -274,73 +266,17 @@ int find_spec(const Dims& d, const int* dof_parentid) {
   return 0;
 }
 
-// Diagnostic: MJX355_LDS_PAD=<bytes> (all phases) or MJX355_LDS_PAD<ph>=<bytes> (phase 0/1/2)
-// adds unused dynamic LDS per world, to measure how throughput depends on resident worlds
-// per CU.
-static size_t lds_bytes(const Params& host, int ph) {
-  static const long pad[3] = {[] { const char* e = getenv("MJX355_LDS_PAD0"); return e ? atol(e) : 0L; }(),
-                              [] { const char* e = getenv("MJX355_LDS_PAD1"); return e ? atol(e) : 0L; }(),
-                              [] { const char* e = getenv("MJX355_LDS_PAD2"); return e ? atol(e) : 0L; }()};
-  static const long pad_all = [] {
-    const char* e = getenv("MJX355_LDS_PAD");
-    return e ? atol(e) : 0L;
-  }();
-  const long p = pad_all + pad[ph >= 3 ? 1 : ph];
-  const Lds& L = ph == kLdsJG ? host.LPJ : host.LP[ph];
-  return (size_t)L.total * 4 + (size_t)(p > 0 ? p : 0);
-}
-
-// dynamic LDS of step_resolve: the largest of the three phase carves
-static size_t lds_resolve(const Params& host) {
-  return std::max(lds_bytes(host, 0), std::max(lds_bytes(host, 1), lds_bytes(host, 2)));
-}
-// dynamic LDS of a class chain (step_chain): the class's Newton carve, phase C's and, when it
-// runs the next phase A, phase A's
-static size_t lds_chain(const Params& host, int cls, bool with_a, bool jg = false) {
-  size_t b = std::max(lds_bytes(host, cls ? 2 + cls : jg ? kLdsJG : 1), lds_bytes(host, 2));
-  return with_a ? std::max(b, lds_bytes(host, 0)) : b;
-}
-// Which class chains run as one launch (step_chain).  Default: the bulk class (the fewest
-// rows, most worlds, on the launch stream) when the batch is at most kChainMaxWorlds.
-// Measured (G1 4,096, two interleaved rounds on one box): bulk chained 2.81 M env-steps/s,
-// every class chained 2.70 M, none 2.67 M, only the heavy classes 2.58 M -- the heavy class's
-// latency kernel then runs its C and next A at one wave per SIMD; jump hfield at 16,384
-// worlds (five residency rounds, whose per-slot sums already average the Newton tails):
-// none 4.54 M, bulk 4.52 M, all 4.44 M.  MJX355_CHAIN (A/B diagnostic): 0 none, 1 every
-// class, 2 the bulk class at any batch size, 3 only the others.
-constexpr int kChainMaxWorlds = 8192;
-// J-in-global mode of the full-capacity class (newton_jg): by default the throughput form past
-// kChainMaxWorlds worlds, where that class holds thousands of worlds and its launch is
-// throughput-bound by its LDS carve (jump hfield 16,384: ~5,400 worlds at 84-137 rows, 4 per CU
-// with J in LDS, 12 per CU without; 4.64 -> 4.80 M env-steps/s, two interleaved rounds), and
-// off below (G1 4,096: ~670 heavy worlds, one per SIMD at most: +-0.5 %; tracking -1 %)
-static int jg_mode(int nworld) {
-  const int m = newton_jg();
-  return m >= 0 ? m : nworld > kChainMaxWorlds ? 2 : 0;
-}
-static bool chain_env(int cls, int nworld) {
-  static const int mode = [] {
-    const char* e = getenv("MJX355_CHAIN");
-    return e ? atoi(e) : -1;
-  }();
-  if (mode < 0) return cls == 1 && nworld <= kChainMaxWorlds;
-  return mode == 1 || (mode == 2 && cls == 1) || (mode == 3 && cls != 1);
-}
-
+// One-time kernel attributes: the dynamic-LDS limit of every step kernel whose launches can ask
+// for more than the 64 KiB default, from the launches' own rule (lds_need).  The J-in-global
+// Newton kernels never pass it (15,904 B at nv 64 and 256 rows, the largest the engine admits:
+// tests/carve_invariants.cpp).  The chains also hold phases C and A, whose carve grows with the
+// geoms that keep an LDS frame (152,176 B found among admitted models), and kPhNewtonLatCap the
+// full fast carve (54,944 B at its default of at most 160 rows, 81,440 B at 256 rows when
+// MJX355_HEAVY_CAP forces it).
 hipError_t prepare_step(const Params& host) {
-  size_t shmem[3] = {lds_bytes(host, 0), lds_bytes(host, 1), lds_bytes(host, 2)};
-  for (int k = 0; k < host.nrowclass; k++) shmem[1] = std::max(shmem[1], lds_bytes(host, 3 + k));
-  // Codes 9 and 10 run in the J-in-global carve, which never passes the 64 KiB default (15,904
-  // B at nv 64 and 256 rows, the largest the engine admits: tests/carve_invariants.cpp).  Code
-  // 11's chain also holds phases C and A, whose carve grows with the geoms that keep an LDS
-  // frame (152,176 B found among admitted models), and code 12 the full fast carve (54,944 B
-  // at its default of at most 160 rows, 81,440 B at 256 rows when MJX355_HEAVY_CAP forces it).
-  for (int ph = 0; ph < 13; ph++) {  // phase codes of phase_kernel
-    const size_t need = ph == 9 || ph == 10 ? lds_bytes(host, kLdsJG)
-                        : ph == 12          ? shmem[1]
-                        : ph >= 5           ? std::max(shmem[0], std::max(shmem[1], shmem[2]))
-                                            : shmem[ph == 3 ? 1 : ph == 4 ? 0 : ph];
-    const StepFn f = step_fn(host, ph);
+  for (int ph = 0; ph < kPhaseCodes; ph++) {
+    const size_t need = lds_need_max(host, knobs(), PhaseCode(ph));
+    const StepFn f = step_fn(host, PhaseCode(ph));
     if (need > 64 * 1024 && f) {
       hipError_t e = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)need);
@@ -348,6 +284,66 @@ hipError_t prepare_step(const Params& host) {
     }
   }
   return hipSuccess;
+}
+
+// ------------------------------------------------------------------ batch split fork / join
+// Batch split: the worlds in nsplit contiguous ranges, each range's A -> B -> C chain on its
+// own stream (split 0 on the launch stream).  The ranges are independent, so one range's
+// launches fill the tail of the other's (the last, partly filled round of workgroups per CU)
+// and the launch gaps.  Measured: Go1 8192 worlds 4.91 -> 5.61 M env-steps/s at 2 splits (3:
+// 5.47, 4: 5.38).  With row classes: launch_split_classes (flat fork / join); the default for
+// those models is one split (capi.cpp).  Masked forwards (reset worlds) stay one launch set.
+struct Splits {
+  int n;
+  int wb[kMaxSplit + 1];  // split k: worlds [wb[k], wb[k + 1])
+  hipStream_t st[kMaxSplit];
+};
+static Splits make_splits(int nworld, int nsplit, hipStream_t stream, const SideStream* side) {
+  Splits s;
+  s.n = nsplit;
+  for (int k = 0; k <= nsplit; k++) s.wb[k] = (int)(((long long)nworld * k) / nsplit);
+  for (int k = 0; k < nsplit; k++) s.st[k] = k == 0 ? stream : side->split[k];
+  return s;
+}
+// Fork: the split streams, and the first `nc` class streams of every split, wait for the
+// launch stream.
+static hipError_t fork_splits(const Splits& s, const SideStream* side, int nc) {
+  hipError_t e = hipEventRecord(side->split_fork, s.st[0]);
+  for (int k = 1; k < s.n && e == hipSuccess; k++) e = hipStreamWaitEvent(s.st[k], side->split_fork, 0);
+  for (int k = 0; k < s.n; k++)
+    for (int c = 0; c < nc && e == hipSuccess; c++)
+      e = hipStreamWaitEvent(side->stream[k][c], side->split_fork, 0);
+  return e;
+}
+// Join: the launch stream waits for those class streams, then for the split streams.
+static hipError_t join_splits(const Splits& s, const SideStream* side, int nc) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < s.n; k++)
+    for (int c = 0; c < nc && e == hipSuccess; c++) {
+      e = hipEventRecord(side->join[k][c], side->stream[k][c]);
+      if (e == hipSuccess) e = hipStreamWaitEvent(s.st[0], side->join[k][c], 0);
+    }
+  for (int k = 1; k < s.n && e == hipSuccess; k++) {
+    e = hipEventRecord(side->split_join[k], s.st[k]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s.st[0], side->split_join[k], 0);
+  }
+  return e;
+}
+
+// Row class `cls` of W on stream cs, one substep: its Newton launch `ch`, then (piped) phase C
+// and the next substep's phase A (`nx`) of the same worlds -- all in one launch (step_chain)
+// where `ch` is chained.
+static void issue_class(const Worlds& W, const LaunchChoice& ch, int cls, bool piped, hipStream_t cs,
+                        int last, const NextSubstep& nx, int integrate) {
+  const int csel = W.k | (cls + 1) << 8;
+  if (ch.chained) {
+    launch(W, ch.code, cls, !last, cs, csel | (last ? 0 : kSelChainA) | nx.chain_sel(), last, integrate);
+    return;
+  }
+  launch(W, ch.code, cls, false, cs, W.k | ch.sel, last, cls);
+  if (!piped) return;
+  launch(W, kPhC, 0, false, cs, csel | ch.sel, last, integrate);
+  if (!last) launch(W, kPhA, 0, false, cs, csel | nx.apar | ch.sel, nx.last, integrate);
 }
 
 // Batch split together with Newton row classes: every fork starts from the launch stream
@@ -359,78 +355,41 @@ hipError_t prepare_step(const Params& host) {
 // bundles (a synthetic probe with no engine code reproduces it in a torch process and not
 // standalone on ROCm 7.2: scripts/capture_probe*.{hip,py}), and the
 // flat form keeps the capture to the fork / join shape the unsplit class path uses.
-static hipError_t launch_split_classes(const Params& host, const Params* dev, int nworld,
-                                       int nsubstep, int integrate, hipStream_t stream,
-                                       const SideStream* side, int nsplit, bool piped) {
-  const StepFn fA = step_fn(host, 0), fB = step_fn(host, 1), fC = step_fn(host, 2);
-  const StepFn fBL = newton_lat() ? step_fn(host, 3) : fB;
-  const int cBL = newton_lat() ? 3 : 1;  // fBL's phase code
+// A diagnostic topology: the plain class launches only (class_choice_plain), no overflow lists.
+static hipError_t launch_split_classes(const Params& host, const Params* dev, int nsubstep,
+                                       int integrate, const Splits& s, const SideStream* side,
+                                       bool piped) {
   const int nc = host.nrowclass;
-  hipStream_t sst[kMaxSplit];
-  int wb[kMaxSplit + 1];
-  for (int k = 0; k <= nsplit; k++) wb[k] = (int)(((long long)nworld * k) / nsplit);
-  sst[0] = stream;
-  for (int k = 1; k < nsplit; k++) sst[k] = side->split[k];
   hipError_t e = hipSuccess;
-  auto fork_all = [&](bool classes) {
-    e = hipEventRecord(side->split_fork, stream);
-    for (int k = 1; k < nsplit && e == hipSuccess; k++) e = hipStreamWaitEvent(sst[k], side->split_fork, 0);
-    for (int k = 0; k < nsplit && classes; k++)
-      for (int c = 0; c < nc && e == hipSuccess; c++)
-        e = hipStreamWaitEvent(side->stream[k][c], side->split_fork, 0);
-    return e;
-  };
-  auto join_all = [&](bool classes) {
-    for (int k = 0; k < nsplit && classes; k++)
-      for (int c = 0; c < nc && e == hipSuccess; c++) {
-        e = hipEventRecord(side->join[k][c], side->stream[k][c]);
-        if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->join[k][c], 0);
-      }
-    for (int k = 1; k < nsplit && e == hipSuccess; k++) {
-      e = hipEventRecord(side->split_join[k], sst[k]);
-      if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->split_join[k], 0);
-    }
-    return e;
-  };
   for (int sub = 0; sub < nsubstep; sub++) {
     const int last = sub == nsubstep - 1;
-    if (fork_all(false) != hipSuccess) return e;
-    for (int k = 0; k < nsplit; k++) {
-      const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
-      if (n <= 0) continue;
-      if (!piped || sub == 0)
-        MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), sst[k], dev, w0, w1, k, last, integrate,
-                   nullptr);
-      MJX_LAUNCH_CLASSIFY(sst[k], dev, w0, w1,
-                         k, nullptr);
+    const NextSubstep nx{0, sub + 1 == nsubstep - 1};  // (no overflow lists: no parity bit)
+    if ((e = fork_splits(s, side, 0)) != hipSuccess) return e;
+    for (int k = 0; k < s.n; k++) {
+      const Worlds W{host, dev, k, s.wb[k], s.wb[k + 1], nullptr};
+      if (W.w1 <= W.w0) continue;
+      if (!piped || sub == 0) launch(W, kPhA, 0, false, s.st[k], k, last, integrate);
+      MJX_LAUNCH_CLASSIFY(s.st[k], dev, W.w0, W.w1, k, nullptr);
     }
-    if (join_all(false) != hipSuccess || fork_all(true) != hipSuccess) return e;
-    for (int k = 0; k < nsplit; k++) {
-      const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
-      if (n <= 0) continue;
-      auto class_chain = [&](hipStream_t cs, int cls) {
-        MJX_LAUNCH(cls ? 1 : cBL, cls ? fB : fBL, dim3(n), lds_bytes(host, cls ? 2 + cls : 1), cs, dev,
-                   w0, w1, k, last, cls, nullptr);
-        if (!piped) return;
-        MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), cs, dev, w0, w1, k | (cls + 1) << 8, last,
-                   integrate, nullptr);
-        if (!last)
-          MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), cs, dev, w0, w1, k | (cls + 1) << 8,
-                     sub + 1 == nsubstep - 1, integrate, nullptr);
-      };
-      for (int c = 0; c < nc; c++) class_chain(side->stream[k][c], c == 0 ? 0 : nc + 1 - c);
-      class_chain(sst[k], 1);
+    if ((e = join_splits(s, side, 0)) != hipSuccess || (e = fork_splits(s, side, nc)) != hipSuccess)
+      return e;
+    for (int k = 0; k < s.n; k++) {
+      const Worlds W{host, dev, k, s.wb[k], s.wb[k + 1], nullptr};
+      if (W.w1 <= W.w0) continue;
+      for (int c = 0; c <= nc; c++) {  // classes 0, nc, nc - 1, ..., 2, then 1 on the split stream
+        const int cls = c == 0 ? 0 : nc + 1 - c;
+        issue_class(W, class_choice_plain(knobs(), cls), cls, piped,
+                    c < nc ? side->stream[k][c] : s.st[k], last, nx, integrate);
+      }
     }
-    if (join_all(true) != hipSuccess) return e;
+    if ((e = join_splits(s, side, nc)) != hipSuccess) return e;
     if (piped) continue;
-    if (fork_all(false) != hipSuccess) return e;
-    for (int k = 0; k < nsplit; k++) {
-      const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
-      if (n > 0)
-        MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), sst[k], dev, w0, w1, k, last, integrate,
-                   nullptr);
+    if ((e = fork_splits(s, side, 0)) != hipSuccess) return e;
+    for (int k = 0; k < s.n; k++) {
+      const Worlds W{host, dev, k, s.wb[k], s.wb[k + 1], nullptr};
+      if (W.w1 > W.w0) launch(W, kPhC, 0, false, s.st[k], k, last, integrate);
     }
-    if (join_all(false) != hipSuccess) return e;
+    if ((e = join_splits(s, side, 0)) != hipSuccess) return e;
   }
   return hipGetLastError();
 }
@@ -448,29 +407,18 @@ static void ovf_chain(const Params& host, const Params* dev, const Params& hbig,
   // the grid: kOvfGrid on a stream of its own (sized for heavy overflow; an empty list costs
   // the same at 1 or 256 workgroups there), kOvfGridInline where the chain runs in line on
   // the critical path (split batches: 256 max-carve workgroups per launch cost Go1 8 %;
-  // engine.h kOvfGridInline);
-  // MJX355_OVF_GRID overrides both
-  static const int grid_env = [] {
-    const char* e = getenv("MJX355_OVF_GRID");
-    return e && atoi(e) > 0 ? atoi(e) : 0;
-  }();
+  // engine.h kOvfGridInline); MJX355_OVF_GRID overrides both
+  const int grid_env = knobs().ovf_grid;
   const int g = std::min(hbig.ovf_cap, grid_env > 0 ? grid_env : in_line ? kOvfGridInline : kOvfGrid);
   const int sel = k | kSelOvf | (par ? kSelRPar : 0);
   const bool next = next_a && !last;
-  MJX_LAUNCH(5, step_fn(hbig, 5), dim3(g), lds_resolve(hbig), cs, dbig, w0, w1,
-             sel | (next ? 0 : kSelClr), last, integrate, nullptr);
-  if (next)
-    MJX_LAUNCH(4, step_fn(host, 4), dim3(g), lds_bytes(host, 0), cs, dev, w0, w1,
-               sel | kSelClr | ((sub + 1) & 1 ? kSelAPar : 0), sub + 1 == nsubstep - 1, integrate,
-               nullptr);
-}
-
-static bool ovf_stream_env() {
-  static const bool on = [] {
-    const char* e = getenv("MJX355_OVF_STREAM");
-    return e && atoi(e) != 0;
-  }();
-  return on;
+  launch(Worlds{hbig, dbig, k, w0, w1, nullptr}, kPhResolve, 0, false, cs, sel | (next ? 0 : kSelClr),
+         last, integrate, g);
+  if (next) {
+    const NextSubstep nx = next_substep(sub, nsubstep);
+    launch(Worlds{host, dev, k, w0, w1, nullptr}, kPhOvfNextA, 0, false, cs, sel | kSelClr | nx.apar,
+           nx.last, integrate, g);
+  }
 }
 
 // Order of the concurrent branches in a captured graph.  Graph replay (ROCm 7 clr) keeps the
@@ -484,264 +432,183 @@ static bool ovf_stream_env() {
 // full class's long-latency worlds then start behind the bulk chain's and end last.
 // MJX355_MAIN_FIRST=0 / 1 forces it off / on.
 static bool main_first(hipStream_t st) {
-  static const int mode = [] {
-    const char* e = getenv("MJX355_MAIN_FIRST");
-    return e ? atoi(e) : -1;
-  }();
+  const int mode = knobs().main_first;
   if (mode >= 0) return mode != 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+}
+
+// ------------------------------------------------------------------------------ launch_step
+// What the launches of one launch_step call share, and one batch range at one substep.
+struct StepCtx {
+  const Params& host;
+  const Params* dev;
+  const Params* hbig;  // the max-capacity Params of the overflow re-solve, or null
+  const Params* dbig;
+  const SideStream* side;
+  const uint8_t* mask;
+  int nworld, nsubstep, integrate, nsplit;
+  bool ovf;            // the re-solve chain runs (host.ovf_resolve, hbig and side present)
+  bool piped;          // row classes: each class's C and next A behind its Newton (class_pipe)
+  LaunchChoice flat;   // no row classes: the range's Newton launch or range chain
+  MaskedChoice masked; // mask present: the masked forward's Newton launch
+};
+struct Range {
+  Worlds W;
+  hipStream_t st;
+  int sub;
+};
+static void range_ovf_chain(const StepCtx& c, const Range& r, hipStream_t cs, bool next_a, bool in_line) {
+  ovf_chain(c.host, c.dev, *c.hbig, c.dbig, cs, r.W.k, r.W.w0, r.W.w1, r.sub, c.nsubstep, c.integrate,
+            next_a, in_line);
+}
+// The re-solve chain of a range on a stream of its own (side->ovf[k]): forked after the
+// substep's phase A (and classify), joined at the end of the substep -- the empty chain
+// overlaps the range's launches.  (Record the fork before the stream's next launch; launch
+// the chain after it while capturing: main_first.)
+static hipError_t ovf_fork_launch(const StepCtx& c, const Range& r, bool next_a) {
+  hipError_t e = hipStreamWaitEvent(c.side->ovf[r.W.k], c.side->ovf_fork[r.W.k], 0);
+  if (e == hipSuccess) range_ovf_chain(c, r, c.side->ovf[r.W.k], next_a, false);
+  return e;
+}
+static hipError_t ovf_join(const StepCtx& c, const Range& r) {
+  hipError_t e = hipEventRecord(c.side->ovf_join[r.W.k], c.side->ovf[r.W.k]);
+  return e == hipSuccess ? hipStreamWaitEvent(r.st, c.side->ovf_join[r.W.k], 0) : e;
+}
+
+// The masked forward in the max carve (masked_choice): one launch, or A / latency Newton / C.
+static hipError_t launch_masked_max(const StepCtx& c, hipStream_t stream) {
+  const Worlds W{*c.hbig, c.dbig, 0, 0, c.nworld, c.mask};
+  const LaunchChoice& ch = c.masked.newton;
+  if (!ch.chained) launch(W, kPhA, 0, false, stream, 0, 1, c.integrate);
+  launch(W, ch.code, 0, false, stream, 0, 1, ch.chained ? c.integrate : -1);
+  if (!ch.chained) launch(W, kPhC, 0, false, stream, 0, 1, c.integrate);
+  return hipGetLastError();
+}
+
+// One substep of a range with row classes, behind its phase A.  Row-class pipelines (one
+// split): each class's Newton launch is followed on the same stream by its phase C and then by
+// the next substep's phase A for the same worlds, so the bulk class's C and next A overlap the
+// heavy class's Newton tail; the streams join before the next classify.  MJX355_CLASS_PIPE=0:
+// phase C / A over every world after the join (diagnostic).
+static hipError_t substep_classes(const StepCtx& c, const Range& r) {
+  const Worlds& W = r.W;
+  const int k = W.k, nc = c.host.nrowclass, last = r.sub == c.nsubstep - 1;
+  hipError_t e = hipSuccess;
+  if (c.mask) {
+    // masked forward in the fast carve: one Newton launch over the masked worlds (masked_choice)
+    launch(W, c.masked.newton.code, 0, false, r.st, k, last, -1);
+    // (MJX355_MASKED_BIG=0) masked worlds past the fast carve: re-solved in line
+    if (c.ovf) range_ovf_chain(c, r, r.st, false, true);
+  } else {
+    MJX_LAUNCH_CLASSIFY(r.st, c.dev, W.w0, W.w1, k, c.mask);
+    // MJX355_OVF_STREAM=1 (diagnostic): the re-solve chain on a stream of its own, forked here
+    // and joined after the class joins
+    const bool ovf_own = c.ovf && knobs().ovf_stream;
+    if (ovf_own && ((e = hipEventRecord(c.side->ovf_fork[k], r.st)) != hipSuccess ||
+                    (e = ovf_fork_launch(c, r, c.piped)) != hipSuccess))
+      return e;
+    // Newton by row class, concurrently: the full-capacity class (few worlds, long
+    // per-world latency) first on a side stream so its blocks dispatch first, the middle
+    // classes on further side streams, the smallest (most worlds) on the launch stream.
+    // Measured: forking the side classes after the smallest makes the full class the tail
+    // (B span 240 -> 255 us, G1).
+    if ((e = hipEventRecord(c.side->fork[k], r.st)) != hipSuccess) return e;
+    const NextSubstep nx = next_substep(r.sub, c.nsubstep);
+    auto issue = [&](hipStream_t cs, int cls) {
+      issue_class(W, class_choice(knobs(), c.host.d.njmax, c.nworld, cls, c.piped), cls, c.piped, cs,
+                  last, nx, c.integrate);
+    };
+    for (int i = 0; i < nc; i++) {
+      hipStream_t cs = c.side->stream[k][i];
+      if ((e = hipStreamWaitEvent(cs, c.side->fork[k], 0)) != hipSuccess) return e;
+      issue(cs, i == 0 ? 0 : nc + 1 - i);  // 0, then nc, nc-1, ..., 2
+      // the re-solve chain behind the full-capacity class (its stream ends well before the
+      // bulk class's), not on a stream of its own: a further concurrent branch crashed
+      // graph replay under torch's HIP runtime (two middle classes + the re-solve stream).
+      // Measured ahead of that class instead: G1 -3 % (its 64 KiB workgroups then take
+      // LDS from the bulk class's first Newton waves)
+      if (i == 0 && c.ovf && !ovf_own) range_ovf_chain(c, r, cs, c.piped, false);
+    }
+    issue(r.st, 1);
+    for (int i = 0; i < nc; i++) {
+      e = hipEventRecord(c.side->join[k][i], c.side->stream[k][i]);
+      if (e == hipSuccess) e = hipStreamWaitEvent(r.st, c.side->join[k][i], 0);
+      if (e != hipSuccess) return e;
+    }
+    if (ovf_own && (e = ovf_join(c, r)) != hipSuccess) return e;
+    if (c.piped) return hipSuccess;
+  }
+  launch(W, kPhC, 0, false, r.st, k, last, c.integrate);
+  return hipSuccess;
+}
+
+// One substep of a range without row classes (Go1), behind its phase A: phase B and C, or the
+// range's B -> C -> next substep's A as one launch (step_chain over every world of the range),
+// as the class pipelines do for a class, when noclass_choice chose it.  Worlds listed for the
+// re-solve skip the chain's B, C and A; the re-solve chain then runs their next A too.
+// The re-solve chain runs on a stream of its own, or in line behind phase C on the split stream
+// of a split batch (a fork from a split stream is a second-level fork, which breaks graph
+// capture; capi.cpp).  Also in line behind a range chain on an unsplit batch: the chain's B, C
+// and fused next A skip the listed worlds by ovf_flag[w], which the re-solve chain's next phase
+// A rewrites, so a concurrent re-solve could clear a flag before the range chain's workgroup
+// for that world reads it and the world would run one extra B -> C -> A.
+static hipError_t substep_flat(const StepCtx& c, const Range& r) {
+  const Worlds& W = r.W;
+  const LaunchChoice& ch = c.flat;
+  const int k = W.k, last = r.sub == c.nsubstep - 1;
+  const bool in_line = c.ovf && (c.nsplit > 1 || ch.chained), forked = c.ovf && !in_line;
+  const bool mfirst = main_first(r.st);
+  hipError_t e = hipSuccess;
+  if (forked && (e = hipEventRecord(c.side->ovf_fork[k], r.st)) != hipSuccess) return e;
+  if (forked && !mfirst && (e = ovf_fork_launch(c, r, ch.chained)) != hipSuccess) return e;
+  if (ch.chained)
+    launch(W, ch.code, 0, !last, r.st,
+           k | (last ? 0 : kSelChainA) | next_substep(r.sub, c.nsubstep).chain_sel(), last, c.integrate);
+  else
+    launch(W, ch.code, 0, false, r.st, k, last, 0);
+  if (forked && mfirst && (e = ovf_fork_launch(c, r, ch.chained)) != hipSuccess) return e;
+  if (!ch.chained) launch(W, kPhC, 0, false, r.st, k, last, c.integrate);
+  if (in_line) range_ovf_chain(c, r, r.st, ch.chained, true);
+  return forked ? ovf_join(c, r) : hipSuccess;
 }
 
 hipError_t launch_step(const Params& host, const Params* dev, int nworld, int nsubstep,
                        int integrate, const uint8_t* mask, hipStream_t stream,
                        const SideStream* side, const Params* hbig, const Params* dbig) {
   if (nworld <= 0) return hipSuccess;
-  // The masked forward (a few reset worlds): its three launches in the max carve, or in the
-  // fast carve with the re-solve in line behind them.  The max-carve grid is the whole batch,
-  // and at 64 KiB of LDS per workgroup even the unmasked workgroups dispatch two per CU; the
-  // in-line re-solve is a fixed launch on the critical path.  Measured: G1 4,096 worlds max
-  // carve +1.1 %, jump hfield 16,384 worlds fast carve +9.5 % (round 6, two interleaved rounds:
-  // +14 %); round 6, max carve (fused, step_masked): Go1 8,192 +1.5 %, rough Go1 +2.0 %, jump
-  // flat 16,384 +0.8 %.  So the max carve unless a heightfield model has more than 4,096
-  // worlds (its reset worlds' phase A at the max carve's 300 contacts is the slow part there).
-  // MJX355_MASKED_BIG=0/1 forces.
-  static const int masked_big_env = [] {
-    const char* e = getenv("MJX355_MASKED_BIG");
-    return e ? atoi(e) : -1;
-  }();
-  const bool masked_big = masked_big_env >= 0 ? masked_big_env != 0 : nworld <= 4096 || host.d.nhfield == 0;
-  if (mask && hbig && masked_big) {
-    // masked forward (a few reset worlds): at full capacity throughout -- nothing to re-solve;
-    // A -> B -> C as one launch (step_masked) unless MJX355_MASKED_FUSED=0
-    static const bool fused = [] {
-      const char* e = getenv("MJX355_MASKED_FUSED");
-      return !e || atoi(e) != 0;
-    }();
-    if (const StepFn fM = fused ? step_fn(*hbig, 8) : nullptr) {
-      MJX_LAUNCH(8, fM, dim3(nworld), lds_resolve(*hbig), stream, dbig, 0, nworld, 0, 1, integrate,
-                 mask);
-      return hipGetLastError();
-    }
-    const StepFn fA = step_fn(*hbig, 0), fBL = step_fn(*hbig, 3), fC = step_fn(*hbig, 2);
-    MJX_LAUNCH(0, fA, dim3(nworld), lds_bytes(*hbig, 0), stream, dbig, 0, nworld, 0, 1, integrate,
-               mask);
-    MJX_LAUNCH(3, fBL, dim3(nworld), lds_bytes(*hbig, 1), stream, dbig, 0, nworld, 0, 1, -1, mask);
-    MJX_LAUNCH(2, fC, dim3(nworld), lds_bytes(*hbig, 2), stream, dbig, 0, nworld, 0, 1, integrate,
-               mask);
-    return hipGetLastError();
-  }
-  const StepFn fA = step_fn(host, 0), fB = step_fn(host, 1), fC = step_fn(host, 2);
-  const StepFn fBL = newton_lat() ? step_fn(host, 3) : fB;
-  const int cBL = newton_lat() ? 3 : 1;  // fBL's phase code
+  const LaunchKnobs& kn = knobs();
   const int nc = host.nrowclass;
-  if (nc > 0 && !side) return hipErrorInvalidValue;
-  const bool ovf = hbig && side && host.ovf_resolve;
-  // Batch split: the worlds in nsplit contiguous ranges, each range's A -> B -> C chain on
-  // its own stream.  The ranges are independent, so one range's launches fill the tail of
-  // the other's (the last, partly filled round of workgroups per CU) and the launch gaps.
-  // Measured: Go1 8192 worlds 4.91 -> 5.61 M env-steps/s at 2 splits (3: 5.47, 4: 5.38).
-  // With row classes: launch_split_classes (flat fork / join); the default for those models
-  // is one split (capi.cpp).  Masked forwards (reset worlds) stay one launch set.
+  // (masked forwards stay one launch set)
   const int nsplit = (!mask && side) ? std::max(1, std::min(side->nsplit, kMaxSplit)) : 1;
-  static const bool pipe = [] {
-    const char* e = getenv("MJX355_CLASS_PIPE");
-    return !e || atoi(e) != 0;
-  }();
-
+  const StepCtx c{host, dev, hbig, dbig, side, mask, nworld, nsubstep, integrate, nsplit,
+                  /*ovf=*/hbig && side && host.ovf_resolve,
+                  /*piped=*/nc > 0 && !mask && kn.class_pipe,
+                  noclass_choice(kn, side && side->range_chain, mask != nullptr),
+                  masked_choice(kn, host.d.nhfield, nc, nworld, hbig != nullptr)};
+  if (mask && c.masked.max_carve) return launch_masked_max(c, stream);
+  if (nc > 0 && !side) return hipErrorInvalidValue;
+  const Splits s = make_splits(nworld, nsplit, stream, side);
   if (nsplit > 1 && nc > 0) {
     // (diagnostic topology; the overflow re-solve is not wired into it)
-    if (ovf) return hipErrorNotSupported;
-    return launch_split_classes(host, dev, nworld, nsubstep, integrate, stream, side, nsplit, pipe);
+    if (c.ovf) return hipErrorNotSupported;
+    return launch_split_classes(host, dev, nsubstep, integrate, s, side, kn.class_pipe != 0);
   }
-  hipStream_t sst[kMaxSplit];
-  int wb[kMaxSplit + 1];
-  for (int k = 0; k <= nsplit; k++) wb[k] = (int)(((long long)nworld * k) / nsplit);
-  sst[0] = stream;
   hipError_t e = hipSuccess;
-  if (nsplit > 1) {
-    e = hipEventRecord(side->split_fork, stream);
-    for (int k = 1; k < nsplit && e == hipSuccess; k++) {
-      sst[k] = side->split[k];
-      e = hipStreamWaitEvent(sst[k], side->split_fork, 0);
-    }
-    if (e != hipSuccess) return e;
-  }
-  // Row-class pipelines (nc > 0, one split): each class's Newton launch is followed on the
-  // same stream by its phase C and then by the next substep's phase A for the same worlds,
-  // so the bulk class's C and next A overlap the heavy class's Newton tail; the streams
-  // join before the next classify.  MJX355_CLASS_PIPE=0: phase C / A over every world
-  // after the join (diagnostic).
-  // Models without row classes (Go1): each range's B -> C -> next substep's A as one launch
-  // (step_chain over every world of the range), as the class pipelines do for a class, when
-  // range_chain_default chose it.  Worlds listed for the re-solve skip the chain's B, C and
-  // A; the re-solve chain then runs their next A too.  MJX355_RANGE_CHAIN=0/1 forces (A/B).
-  static const int range_chain_env = [] {
-    const char* e = getenv("MJX355_RANGE_CHAIN");
-    return e ? atoi(e) : -1;
-  }();
-  const bool rchain = range_chain_env >= 0 ? range_chain_env != 0 : (side && side->range_chain);
-  const StepFn fR = nc == 0 && !mask && rchain ? step_fn(host, 6) : nullptr;
+  if (nsplit > 1 && (e = fork_splits(s, side, 0)) != hipSuccess) return e;
+  // the next substep's phase A runs behind this one's C (class pipelines, range chain)
+  const bool next_a = c.piped || (nc == 0 && c.flat.chained);
   for (int sub = 0; sub < nsubstep; sub++) {
     const int last = sub == nsubstep - 1;
     const int apar = (sub & 1) ? kSelAPar : 0;  // phase A of this substep lists into parity sub & 1
     for (int k = 0; k < nsplit; k++) {
-      const int w0 = wb[k], w1 = wb[k + 1], n = w1 - w0;
-      if (n <= 0) continue;
-      hipStream_t st = sst[k];
-      const bool piped = nc > 0 && !mask && pipe;
-      const bool nexta = piped || fR;  // the next substep's phase A runs behind this one's C
-      if (!nexta || sub == 0)
-        MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), st, dev, w0, w1, k | apar, last, integrate,
-                   mask);
-      // the re-solve chain: forked after this substep's phase A (and classify), joined at the
-      // end of the substep -- the empty chain overlaps the class launches
-      // split batches: in line behind phase C on the split stream (a fork from a split
-      // stream is a second-level fork, which breaks graph capture; capi.cpp).  Also in line
-      // behind a range chain on an unsplit batch: the chain's B, C and fused next A skip the
-      // listed worlds by ovf_flag[w], which the re-solve chain's next phase A rewrites, so a
-      // concurrent re-solve could clear a flag before the range chain's workgroup for that
-      // world reads it and the world would run one extra B -> C -> A.
-      const bool ovf_inline = ovf && (nsplit > 1 || fR != nullptr);
-      // (record the fork before the stream's next launch; launch the chain after it while
-      // capturing: main_first)
-      auto ovf_record = [&]() {
-        if (!ovf || ovf_inline) return hipSuccess;
-        return hipEventRecord(side->ovf_fork[k], st);
-      };
-      auto ovf_launch = [&]() {
-        if (!ovf || ovf_inline) return hipSuccess;
-        hipError_t e2 = hipStreamWaitEvent(side->ovf[k], side->ovf_fork[k], 0);
-        if (e2 == hipSuccess)
-          ovf_chain(host, dev, *hbig, dbig, side->ovf[k], k, w0, w1, sub, nsubstep, integrate,
-                    nexta, false);
-        return e2;
-      };
-      auto fork_ovf = [&]() {
-        hipError_t e2 = ovf_record();
-        return e2 == hipSuccess ? ovf_launch() : e2;
-      };
-      const bool mfirst = main_first(st);
-      auto join_ovf = [&]() {
-        if (!ovf) return hipSuccess;
-        if (ovf_inline) {
-          ovf_chain(host, dev, *hbig, dbig, st, k, w0, w1, sub, nsubstep, integrate, fR != nullptr, true);
-          return hipSuccess;
-        }
-        hipError_t e2 = hipEventRecord(side->ovf_join[k], side->ovf[k]);
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(st, side->ovf_join[k], 0);
-        return e2;
-      };
-      if (nc > 0 && mask) {
-        // masked forward (a few reset worlds): one Newton launch at full capacity over the
-        // masked worlds -- no classify launch, no fork/join latency on this short critical path
-        // The grid is the whole batch and nearly every workgroup exits at once, so the launch
-        // costs its dispatch rounds: with J read from the B pack in global memory (carve kLdsJG,
-        // ~8 KB instead of the full fast carve's 31.8 KB) 16 workgroups fit a CU instead of 4.
-        // MJX355_MASKED_JG=0: J in LDS (A/B)
-        static const bool masked_jg = [] {
-          const char* e = getenv("MJX355_MASKED_JG");
-          return !e || atoi(e) != 0;
-        }();
-        const StepFn fMJ = masked_jg && newton_lat() ? step_fn(host, 9) : nullptr;
-        MJX_LAUNCH(fMJ ? 9 : cBL, fMJ ? fMJ : fBL, dim3(n), lds_bytes(host, fMJ ? kLdsJG : 1), st,
-                   dev, w0, w1, k, last, -1, mask);
-        // (MJX355_MASKED_BIG=0) masked worlds past the fast carve: re-solved in line
-        if (ovf) ovf_chain(host, dev, *hbig, dbig, st, k, w0, w1, sub, nsubstep, integrate, false, true);
-      } else if (nc > 0) {
-        MJX_LAUNCH_CLASSIFY(st, dev, w0, w1,
-                           k, mask);
-        // MJX355_OVF_STREAM=1 (diagnostic, scripts/capture_probe*): the re-solve chain on a
-        // stream of its own, forked here and joined after the class joins -- round 4's
-        // topology, kept to reproduce its graph-replay crash
-        if (ovf_stream_env() && (e = fork_ovf()) != hipSuccess) return e;
-        // Newton by row class, concurrently: the full-capacity class (few worlds, long
-        // per-world latency) first on a side stream so its blocks dispatch first, the middle
-        // classes on further side streams, the smallest (most worlds) on the launch stream.
-        // Measured: forking the side classes after the smallest makes the full class the tail
-        // (B span 240 -> 255 us, G1).
-        e = hipEventRecord(side->fork[k], st);
-        if (e != hipSuccess) return e;
-        // class c's stream: B, then (piped) C and the next substep's A of the same worlds --
-        // as one launch (step_chain) unless MJX355_CHAIN=0
-        auto class_chain = [&](hipStream_t cs, int cls) {
-          const bool cjg = cls == 0 && newton_lat() && jg_mode(nworld) == 1;
-          const int cX = cls == 0 && newton_lat() ? (cjg ? 11 : 7) : 6;
-          const StepFn fX = piped && chain_env(cls, nworld) ? step_fn(host, cX) : nullptr;
-          if (fX) {
-            const int selx = k | (cls + 1) << 8 | (last ? 0 : kSelChainA) |
-                             (((sub + 1) & 1) ? kSelAPar : 0) |
-                             (sub + 1 == nsubstep - 1 ? kSelNextLast : 0);
-            MJX_LAUNCH(cX, fX, dim3(n), lds_chain(host, cls, !last, cjg), cs, dev, w0, w1, selx,
-                       last, integrate, mask);
-            return;
-          }
-          const int jg = cls == 0 ? jg_mode(nworld) : 0;
-          const StepFn fJ = jg == 1 && newton_lat() ? step_fn(host, 9) : jg == 2 ? step_fn(host, 10) : nullptr;
-          const StepFn fBH = cls == 0 && !fJ && heavy_cap(host) && newton_lat() ? step_fn(host, 12) : fBL;
-          const int pr = fBH != fBL ? kSelPrio : 0;
-          const int cB = cls ? 1 : fJ ? (jg == 2 ? 10 : 9) : fBH != fBL ? 12 : cBL;
-          MJX_LAUNCH(cB, cls ? fB : fJ ? fJ : fBH, dim3(n),
-                     lds_bytes(host, cls ? 2 + cls : fJ ? kLdsJG : 1), cs, dev, w0, w1, k | pr, last,
-                     cls, mask);
-          if (!piped) return;
-          MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), cs, dev, w0, w1, k | (cls + 1) << 8 | pr,
-                     last, integrate, mask);
-          if (!last)
-            MJX_LAUNCH(0, fA, dim3(n), lds_bytes(host, 0), cs, dev, w0, w1,
-                       k | (cls + 1) << 8 | (((sub + 1) & 1) ? kSelAPar : 0) | pr,
-                       sub + 1 == nsubstep - 1, integrate, mask);
-        };
-        for (int c = 0; c < nc; c++) {
-          const int cls = c == 0 ? 0 : nc + 1 - c;  // 0, then nc, nc-1, ..., 2
-          e = hipStreamWaitEvent(side->stream[k][c], side->fork[k], 0);
-          if (e != hipSuccess) return e;
-          class_chain(side->stream[k][c], cls);
-          // the re-solve chain behind the full-capacity class (its stream ends well before the
-          // bulk class's), not on a stream of its own: a further concurrent branch crashed
-          // graph replay under torch's HIP runtime (two middle classes + the re-solve stream).
-          // Measured ahead of that class instead: G1 -3 % (its 64 KiB workgroups then take
-          // LDS from the bulk class's first Newton waves)
-          if (c == 0 && ovf && !ovf_stream_env())
-            ovf_chain(host, dev, *hbig, dbig, side->stream[k][0], k, w0, w1, sub, nsubstep,
-                      integrate, piped, false);
-        }
-        class_chain(st, 1);
-        for (int c = 0; c < nc; c++) {
-          e = hipEventRecord(side->join[k][c], side->stream[k][c]);
-          if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join[k][c], 0);
-          if (e != hipSuccess) return e;
-        }
-        if (ovf_stream_env() && (e = join_ovf()) != hipSuccess) return e;
-        if (piped) continue;
-      } else if (fR) {
-        if ((e = ovf_record()) != hipSuccess) return e;
-        if (!mfirst && (e = ovf_launch()) != hipSuccess) return e;
-        const int selx = k | (last ? 0 : kSelChainA) | (((sub + 1) & 1) ? kSelAPar : 0) |
-                         (sub + 1 == nsubstep - 1 ? kSelNextLast : 0);
-        MJX_LAUNCH(6, fR, dim3(n), lds_chain(host, 0, !last), st, dev, w0, w1, selx, last,
-                   integrate, mask);
-        if (mfirst && (e = ovf_launch()) != hipSuccess) return e;
-        if ((e = join_ovf()) != hipSuccess) return e;
-        continue;
-      } else {
-        if ((e = ovf_record()) != hipSuccess) return e;
-        if (!mfirst && (e = ovf_launch()) != hipSuccess) return e;
-        // (MJX355_NEWTON_JG=2 on a model without row classes: J from global memory as well)
-        const StepFn fBJ = newton_jg() == 2 ? step_fn(host, 10) : nullptr;  // (A/B only)
-        MJX_LAUNCH(fBJ ? 10 : 1, fBJ ? fBJ : fB, dim3(n), lds_bytes(host, fBJ ? kLdsJG : 1), st, dev,
-                   w0, w1, k, last, 0, mask);
-        if (mfirst && (e = ovf_launch()) != hipSuccess) return e;
-      }
-      MJX_LAUNCH(2, fC, dim3(n), lds_bytes(host, 2), st, dev, w0, w1, k, last, integrate, mask);
-      if (nc == 0 && (e = join_ovf()) != hipSuccess) return e;
+      const Range r{Worlds{host, dev, k, s.wb[k], s.wb[k + 1], mask}, s.st[k], sub};
+      if (r.W.w1 <= r.W.w0) continue;
+      if (!next_a || sub == 0) launch(r.W, kPhA, 0, false, r.st, k | apar, last, integrate);
+      if ((e = nc > 0 ? substep_classes(c, r) : substep_flat(c, r)) != hipSuccess) return e;
     }
   }
-  for (int k = 1; k < nsplit; k++) {
-    e = hipEventRecord(side->split_join[k], sst[k]);
-    if (e == hipSuccess) e = hipStreamWaitEvent(stream, side->split_join[k], 0);
-    if (e != hipSuccess) return e;
-  }
+  if ((e = join_splits(s, side, 0)) != hipSuccess) return e;
   return hipGetLastError();
 }
 
@@ -766,12 +633,12 @@ int lds_residency(size_t bytes) {
 // terrain collision, whose long per-world phase-A tails the chain's per-world flow absorbs;
 // a flat range needing a second round loses the cheap phases' residency.
 bool range_chain_default(const Params& host, int nworld, int nsplit) {
-  const StepFn f = step_fn(host, 6);
+  const StepFn f = step_fn(host, kPhChain);
   hipFuncAttributes fa;
   if (!f || hipFuncGetAttributes(&fa, (const void*)f) != hipSuccess) return false;
   const int regs = (fa.numRegs + 7) & ~7;
   const int per_cu = std::min(4 * (regs > 0 ? std::min(8, 512 / regs) : 8),
-                              lds_residency(lds_chain(host, 0, true)));
+                              lds_residency(lds_need(host, knobs(), kPhChain, 0, true)));
   int dev = 0, ncu = 256;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -796,7 +663,7 @@ int choose_row_classes(const Dims& d, int spec, int (&caps)[kRowClasses]) {
   Params hp{};
   hp.d = d;
   hp.spec = spec;
-  if (hipFuncGetAttributes(&fa, (const void*)step_fn(hp, 1)) != hipSuccess) return 0;
+  if (hipFuncGetAttributes(&fa, (const void*)step_fn(hp, kPhB)) != hipSuccess) return 0;
   // wave64 on gfx950: 512 VGPRs per SIMD lane (granule 8), 4 SIMDs per CU
   const int regs = (fa.numRegs + 7) & ~7;
   const int top = 4 * (regs > 0 ? std::min(8, 512 / regs) : 8);  // register-bound worlds/CU

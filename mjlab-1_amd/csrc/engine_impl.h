@@ -1285,8 +1285,7 @@ template <int SP> constexpr bool kBoxBox = SP == 0 || ModelSpec<SP>::dims().nbox
 // 64 contacts (sim.max_capacity: the reference's njmax bounds a world's contacts too) takes
 // the multi-round forms (rank sort, contacts lane + 64 r)
 template <int SP> constexpr bool kCon1 = SP != 0 && ModelSpec<SP>::dims().nconmax <= kWave;
-// carve index kLdsJG: phase B at full capacity with J in global memory (make_lds jglobal)
-constexpr int kLdsJG = 9;
+// (carve index kLdsJG, engine.h Carve: phase B at full capacity with J in global memory)
 template <int SP, int K> struct SpecLds {
   static constexpr Lds get() {
     constexpr Lds v = make_lds(ModelSpec<SP>::dims(), K == kLdsJG ? 1 : K, K == kLdsJG);
@@ -4060,45 +4059,42 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
 
 using StepFn = void (*)(const Params*, int, int, int, int, int, const uint8_t*);
 
-// kernel of phase code ph: 0 A, 1 B, 2 C, 3 B latency form; 4: phase A over a re-solve list
-// (the fast carve's next substep), 5: a listed world's whole substep (step_resolve); 6 / 7: a
-// row class's B -> C -> next A chain as one launch (step_chain; 7: the latency form); 8: the
-// masked forward's A -> B -> C in the max carve (step_masked)
+// kernel of phase code ph (engine.h PhaseCode); null where the specialisation's role has none
 template <int NR, int SP>
 StepFn phase_kernel(int ph) {
   constexpr int role = SpecRole<SP>::mask;
   switch (ph) {
-    case 0: return step_phase<NR, 0, SP>;
-    case 2: return step_phase<NR, 2, SP>;
-    case 3: return step_newton_lat<NR, SP>;
-    case 4:
+    case kPhA: return step_phase<NR, 0, SP>;
+    case kPhC: return step_phase<NR, 2, SP>;
+    case kPhNewtonLat: return step_newton_lat<NR, SP>;
+    case kPhOvfNextA:
       if constexpr ((role & 1) != 0) return step_ovf<NR, 0, SP, false>;
       else return nullptr;
-    case 1:
+    case kPhB:
       if constexpr ((role & 1) != 0) return step_phase<NR, 1, SP>;
       else return nullptr;
-    case 5:
+    case kPhResolve:
       if constexpr ((role & 2) != 0) return step_resolve<NR, SP>;
       else return nullptr;
-    case 6:
+    case kPhChain:
       if constexpr ((role & 1) != 0) return step_chain<NR, SP, false>;
       else return nullptr;
-    case 7:
+    case kPhChainLat:
       if constexpr ((role & 1) != 0) return step_chain<NR, SP, true>;
       else return nullptr;
-    case 8:
+    case kPhMasked:
       if constexpr ((role & 2) != 0) return step_masked<NR, SP>;
       else return nullptr;
-    case 9:
+    case kPhNewtonLatJG:
       if constexpr ((role & 1) != 0) return step_newton_lat<NR, SP, 3>;
       else return nullptr;
-    case 10:  // the full-capacity class's Newton, throughput form, J in global memory
+    case kPhNewtonJG:
       if constexpr ((role & 1) != 0) return step_phase_jg<NR, SP>;
       else return nullptr;
-    case 11:  // the full-capacity class's B -> C -> next A chain, latency form, J in global memory
+    case kPhChainLatJG:
       if constexpr ((role & 1) != 0) return step_chain<NR, SP, 3>;
       else return nullptr;
-    case 12:  // the latency Newton kernel at the throughput register budget (heavy_cap)
+    case kPhNewtonLatCap:
       if constexpr ((role & 1) != 0) return step_newton_lat<NR, SP, 1, 1>;
       else return nullptr;
     default:

@@ -19,6 +19,12 @@ For every csrc/specs.inc entry and a sweep of generic dims (nv 6 .. 64, row capa
 
 and reports the largest dynamic LDS the launches of phase codes 9 - 12 can ask for, which
 decides what csrc/engine.hip prepare_step must raise the 64 KiB default for.
+
+The same program checks the host-only launch decisions of csrc/launch_select.h: that over the
+sweep prepare_step's rule (lds_need_max) covers every launch the selection functions can
+return, the selection's known answers under default knobs, and -- run as `carve_invariants
+select` under each knob environment of tests/test_gpu_kernel_variants.py KNOB_SETS -- that the
+selection names the phase code that test expects to have launched.
 """
 
 import os
@@ -49,10 +55,15 @@ def _build(tmp, extra=(), csrc=CSRC):
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
+def program(tmp_path_factory):
   r, exe = _build(tmp_path_factory.mktemp("carve"))
   assert r.returncode == 0, f"carve_invariants.cpp does not compile:\n{r.stderr[-4000:]}"
-  run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+  return exe
+
+
+@pytest.fixture(scope="module")
+def report(program):
+  run = subprocess.run([program], capture_output=True, text=True, timeout=120)
   lines = run.stdout.strip().splitlines()
   assert lines, run.stderr
   words = lines[-1].split()
@@ -71,13 +82,52 @@ def test_dynamic_lds_of_codes_9_to_12(report):
   """prepare_step raises hipFuncAttributeMaxDynamicSharedMemorySize where a launch can need
   more than the 64 KiB default.  The J-in-global carve (codes 9, 10) never does; the chain of
   code 11 (with phases C and A) and the full fast carve of code 12 can, within the 160 KiB
-  the engine admits -- so prepare_step's loop covers codes 0 - 12."""
+  the engine admits -- so prepare_step's loop covers every phase code, and the program's sweep
+  (test_carve_invariants_hold) finds no launch that asks for more than it raises."""
   _, _, s = report
   assert s["max_jg_bytes"] <= 64 * 1024, s
   assert s["max_cap_bytes"] <= 64 * 1024 < s["max_cap256_bytes"] <= 160 * 1024, s
   assert 64 * 1024 < s["max_chain_jg_bytes"] <= 160 * 1024, s
-  src = open(os.path.join(CSRC, "engine.hip")).read()
-  assert "for (int ph = 0; ph < 13; ph++) {  // phase codes of phase_kernel" in src
+  assert s["launches"] >= 20, s  # the fixed launches and every code the selection can return
+
+
+def _selection(program, knobs):
+  env = {k: v for k, v in os.environ.items() if not k.startswith("MJX355_")}
+  run = subprocess.run([program, "select"], capture_output=True, text=True, timeout=30, env={**env, **knobs})
+  assert run.returncode == 0, run.stderr
+  words = run.stdout.split()
+  return {words[i]: int(words[i + 1]) for i in range(0, len(words), 2)}
+
+
+def _knob_sets():
+  import test_gpu_kernel_variants as variants  # (its tests are GPU tests; the table is plain data)
+  return variants.KNOB_SETS
+
+
+def test_default_selection(program):
+  """test_gpu_kernel_variants.test_baseline_launches: the capped latency Newton for the
+  full-capacity class, the bulk class's chain, the range chain, the masked forward as one launch."""
+  assert _selection(program, {}) == {"cls0": 12, "cls1": 6, "masked_cls": 8, "masked_nocls": 8, "nocls": 6}
+
+
+@pytest.mark.parametrize("knob_set", sorted(_knob_sets()))
+def test_selection_of_knob_set(knob_set, program):
+  """Under each knob environment the selection returns codes the GPU test expects to have
+  launched (for the full-capacity class, the bulk class, the masked forward, a range without
+  classes), none it expects not to have, and the default's where it expects the baseline's."""
+  knobs, _, _, expect = _knob_sets()[knob_set]
+  got, default = _selection(program, knobs), _selection(program, {})
+  for kind, keys in (("cls", {"step": ("cls0", "cls1"), "masked": ("masked_cls",)}),
+                     ("nocls", {"step": ("nocls",), "masked": ("masked_nocls",)})):
+    if kind not in expect:
+      continue
+    for stage, names in keys.items():
+      for name in names:
+        if stage not in expect[kind]:
+          assert got[name] == default[name], (knob_set, name, got)
+          continue
+        ran, not_ran = expect[kind][stage]
+        assert got[name] in ran and got[name] not in not_ran, (knob_set, name, got, sorted(ran))
 
 
 def test_a_moved_jg_offset_is_caught(tmp_path):
