@@ -175,6 +175,50 @@ int mjx_sim_track_air_time(mjxSim* sim, int n, const int32_t* found_adr, float* 
                            float* last_air, float* cur_contact, float* last_contact,
                            float* last_time, void* stream);
 
+/* Explicit actuators inside the step (mjlab_amd/actuator.py: IdealPdActuator,
+ * DcMotorActuator, DelayedActuator).  Actuator u with kind[u] != 0 is a <motor> whose ctrl
+ * the engine computes every substep, in phase A, from the joint's position q and velocity qd
+ * of that substep:
+ *   t = kp (pt - q);  t += kd (vt - qd);  t += ft;
+ *   kind 2 (ideal PD): ctrl = clamp(t, -effort_limit, effort_limit)
+ *   kind 3 (DC motor): r = clamp(qd, -corner_velocity, corner_velocity) / velocity_limit,
+ *     ctrl = clamp(t, max(saturation_effort (-1 - r), -effort_limit),
+ *                     min(saturation_effort (1 - r), effort_limit))
+ *   kind 1 (delayed builtin): ctrl = pt, the position target itself (read late, below),
+ *     which the model's own position / velocity / motor actuator then takes
+ * every operation rounded once, in this order (the torch form computes the same bits).  The
+ * model's ctrlrange / forcerange then apply as to any ctrl, and the last substep of a step
+ * (and a forward) stores the value in data.ctrl.  Kind 0 actuators take data.ctrl as before.
+ * With max_lag[u] > 0 the position target is read `lag` substeps late: lag = min(lag[w,u],
+ * frames pushed since the reset); lag 0 reads position_target, lag k > 0 frame ring_len - k
+ * of the ring.  After every integrated substep (not in a forward) the engine shifts the ring,
+ * appends position_target, counts the push (pushes[w,u], saturating at ring_len) and, where
+ * min_lag[u] < max_lag[u] and hold[w,u] is zero, draws the next substep's lag uniformly on [min_lag, max_lag] from
+ * a hash of (seed, w, group[u], draws[w,u]++): the actuators of a group share their lags.
+ * A reset of a world is the caller's: zero its pushes and hold (and set its lag); draws is never
+ * cleared.  The host tables are copied; the device buffers stay the caller's (float or int32,
+ * [nworld, nu] unless noted), are read at every step, and must outlive the binding -- writing
+ * them (gains, limits, lags) acts on the next step without another call.  A null descriptor
+ * turns the explicit actuators off.  Synchronises. */
+typedef struct mjxActuatorDesc {
+  int32_t nworld, nu;
+  int32_t ring_len;          /* frames per world of `ring`, <= 32; 0 when nothing is delayed */
+  int32_t reserved;
+  const uint8_t* kind;       /* host [nu]: 0 builtin, 1 delayed builtin, 2 ideal PD, 3 DC motor */
+  const uint8_t* min_lag;    /* host [nu], substeps */
+  const uint8_t* max_lag;    /* host [nu], <= ring_len; 0: not delayed */
+  const uint8_t* group;      /* host [nu] */
+  uint64_t seed;
+  const float *kp, *kd, *effort_limit;
+  const float *saturation_effort, *velocity_limit, *corner_velocity; /* kind 3 only */
+  const float *position_target, *velocity_target, *effort_target;
+  float* ring;               /* [nworld, ring_len, nu], oldest frame first */
+  int32_t *lag, *pushes, *draws;
+  const int32_t* hold;       /* nonzero: the lag is pinned, no draw replaces it; may be null */
+} mjxActuatorDesc;
+size_t mjx_actuator_desc_size(void);
+int mjx_sim_set_actuators(mjxSim* sim, const mjxActuatorDesc* desc, void* stream);
+
 /* Diagnostics: per-sim counters as int32[8] written to host `out` ([0] max contacts, [1] max
  * rows seen, [2] contact-overflow, [3] row-overflow, [4] unsupported-pair events -- dropped
  * work --, [5] max Newton iterations, [6] worlds re-solved at the max capacity); synchronises

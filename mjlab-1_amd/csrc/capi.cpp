@@ -89,6 +89,8 @@ struct mjxSim_ {
   int nair = 0;  // contact air-time tracking (mjx_sim_track_air_time)
   int air_found[mjx::kMaxAirSlots] = {};
   float* air_buf[5] = {};
+  bool act_on = false;  // explicit actuators (mjx_sim_set_actuators)
+  mjx::ActParams act{};
   int spec = 0;  // model specialisation in use (mjx::find_spec), 0 = generic kernels
   mjx::SideStream side{};  // streams of the Newton row classes (when classes are used)
   ~mjxSim_() {
@@ -155,6 +157,8 @@ static mjx::Params host_params(const mjxSim_* s) {
   for (int i = 0; i < mjx::kMaxAirSlots; i++) p.air_found[i] = s->air_found[i];
   p.air_cur = s->air_buf[0]; p.air_last = s->air_buf[1]; p.air_cc = s->air_buf[2];
   p.air_lc = s->air_buf[3]; p.air_time = s->air_buf[4];
+  p.act_on = s->act_on ? 1 : 0;
+  p.act = s->act;
   static const int minrows = [] {
     const char* e = getenv("MJX355_STAMP_MINROWS");
     return e ? atoi(e) : 0;
@@ -836,6 +840,67 @@ int mjx_sim_track_air_time(mjxSim* s, int n, const int32_t* found_adr, float* cu
   for (int i = 0; i < mjx::kMaxAirSlots; i++) s->air_found[i] = i < n ? found_adr[i] : 0;
   float* b[5] = {cur_air, last_air, cur_contact, last_contact, last_time};
   for (int i = 0; i < 5; i++) s->air_buf[i] = n > 0 ? b[i] : nullptr;
+  return sync_params(s, stream);
+}
+
+size_t mjx_actuator_desc_size(void) { return sizeof(mjxActuatorDesc); }
+
+int mjx_sim_set_actuators(mjxSim* s, const mjxActuatorDesc* a, void* stream) {
+  if (!a) {  // off: phase A takes every actuator's ctrl as it is
+    if (!s) return fail("null sim");
+    s->act_on = false;
+    s->act = mjx::ActParams{};
+    return sync_params(s, stream);
+  }
+  const char* const who = "mjx_sim_set_actuators: ";
+  // the descriptor's own consistency first (it needs no sim), then its fit to the sim
+  if (a->nworld < 1) return fail(std::string(who) + "nworld < 1");
+  if (a->nu < 1 || a->nu > mjx::kWave) return fail(std::string(who) + "1 <= nu <= 64");
+  if (a->ring_len < 0 || a->ring_len > mjx::kMaxActLag)
+    return fail(std::string(who) + "0 <= ring_len <= 32");
+  if (!a->kind || !a->min_lag || !a->max_lag || !a->group)
+    return fail(std::string(who) + "null kind / min_lag / max_lag / group table");
+  bool any = false, pd = false, dc = false, delayed = false;
+  for (int u = 0; u < a->nu; u++) {
+    const int k = a->kind[u];
+    if (k != mjx::kActBuiltin && k != mjx::kActDelayed && k != mjx::kActIdealPd &&
+        k != mjx::kActDcMotor)
+      return fail(std::string(who) +
+                  "kind must be 0 (builtin), 1 (delayed builtin), 2 (ideal PD) or 3 (DC motor)");
+    if (a->min_lag[u] > a->max_lag[u]) return fail(std::string(who) + "min_lag > max_lag");
+    if (a->max_lag[u] > a->ring_len) return fail(std::string(who) + "max_lag exceeds ring_len");
+    if (k == mjx::kActBuiltin && a->max_lag[u] != 0)
+      return fail(std::string(who) + "a builtin actuator cannot be delayed");
+    any |= k != mjx::kActBuiltin;
+    dc |= k == mjx::kActDcMotor;
+    pd |= k == mjx::kActIdealPd || k == mjx::kActDcMotor;
+    delayed |= a->max_lag[u] > 0;
+  }
+  if (!any) return fail(std::string(who) + "no explicit actuator (pass a null descriptor to turn them off)");
+  if (!a->position_target) return fail(std::string(who) + "null position_target buffer");
+  if (pd && (!a->kp || !a->kd || !a->effort_limit || !a->velocity_target || !a->effort_target))
+    return fail(std::string(who) + "null gain / limit / target buffer");
+  if (dc && (!a->saturation_effort || !a->velocity_limit || !a->corner_velocity))
+    return fail(std::string(who) + "null DC motor buffer");
+  if (delayed && (!a->ring || !a->lag || !a->pushes || !a->draws))
+    return fail(std::string(who) + "null delay buffer");
+  if (!s) return fail(std::string(who) + "null sim");
+  if (a->nworld != s->nworld) return fail(std::string(who) + "nworld differs from the sim's");
+  if (a->nu != s->d.nu) return fail(std::string(who) + "nu differs from the model's");
+  mjx::ActParams p{};
+  for (int u = 0; u < a->nu; u++) {
+    p.kind[u] = a->kind[u]; p.min_lag[u] = a->min_lag[u]; p.max_lag[u] = a->max_lag[u];
+    p.group[u] = a->group[u];
+  }
+  p.ring_len = delayed ? a->ring_len : 0;
+  p.seed = a->seed;
+  p.kp = a->kp; p.kd = a->kd; p.flim = a->effort_limit;
+  p.sat = a->saturation_effort; p.vlim = a->velocity_limit; p.vcorner = a->corner_velocity;
+  p.pt = a->position_target; p.vt = a->velocity_target; p.ft = a->effort_target;
+  p.ring = a->ring; p.lag = a->lag; p.pushes = a->pushes; p.draws = a->draws;
+  p.hold = a->hold;
+  s->act = p;
+  s->act_on = true;
   return sync_params(s, stream);
 }
 

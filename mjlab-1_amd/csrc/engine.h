@@ -155,6 +155,23 @@ constexpr int kRtSpecBase = 1000;
 using StepFnPtr = void (*)(const struct Params*, int, int, int, int, int, const uint8_t*);
 int register_spec(const Dims& d, const int* par, int npar, StepFnPtr (*fn)(int));
 
+// Explicit actuators (include/mjx355.h mjxActuatorDesc): per-actuator kinds and lag ranges,
+// and the torch-owned per-world buffers, each [nworld, nu] but the ring.
+constexpr int kActBuiltin = 0, kActDelayed = 1, kActIdealPd = 2, kActDcMotor = 3;
+constexpr int kMaxActLag = 32;  // frames per world of the delay ring
+struct ActParams {
+  uint8_t kind[kWave];     // actuator u is lane u (nu <= kWave)
+  uint8_t min_lag[kWave], max_lag[kWave];
+  uint8_t group[kWave];    // actuators of one group draw the same lags
+  int ring_len;            // frames per world in `ring` (0: nothing is delayed)
+  unsigned long long seed;
+  const float *kp, *kd, *flim, *sat, *vlim, *vcorner;  // gains, effort limit, DC motor curve
+  const float *pt, *vt, *ft;                           // position / velocity / effort targets
+  float* ring;             // [nworld, ring_len, nu] past position targets, oldest first
+  int *lag, *pushes, *draws;
+  const int* hold;           // nonzero: the lag is pinned, the push draws no new one (may be null)
+};
+
 // Everything a launch needs, resident in device memory (read through the scalar cache
 // instead of occupying ~500 SGPRs of kernarg space).
 struct Params {
@@ -186,6 +203,12 @@ struct Params {
   int nair;
   int air_found[kMaxAirSlots];
   float *air_cur, *air_last, *air_cc, *air_lc, *air_time;
+  // Explicit actuators (mjx_sim_set_actuators): with act_on set, lane u of phase A's
+  // actuation block replaces ctrl[u] of an actuator with act.kind[u] != 0 by the law's torque
+  // (explicit_ctrl in engine_impl.h); with act.ring_len > 0 its position target is read
+  // act lag substeps late from act.ring, which phase C's integration block pushes.
+  int act_on;
+  ActParams act;
   int stamp_minrows;  // diagnostic stamps build: count worlds with at least this many rows
   // Overflow re-solve ("Contact budget"): with ovf_resolve set, a world
   // whose contacts or constraint rows overflow this carve is not truncated -- phase A lists

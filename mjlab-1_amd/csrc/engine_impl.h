@@ -1583,6 +1583,70 @@ __device__ __forceinline__ ActRec load_act(const DModel& m, const float* gear, c
   r.cr0 = crange[2 * u]; r.cr1 = crange[2 * u + 1];
   return r;
 }
+// ---- explicit actuators (mjx_sim_set_actuators; mjlab_amd/actuator.py is the torch form)
+// Correctly rounded fp32 quotient whatever fp32-division flag the build uses: the fp64
+// quotient of two fp32 values rounds to it exactly (53 >= 2 * 24 + 2 significand bits).
+__device__ __forceinline__ float act_div(float x, float y) {
+  return (float)((double)x / (double)y);
+}
+// The torque of explicit actuator u of world w (lane u) from the joint's position q and
+// velocity qd: the operations of IdealPdActuator.compute / DcMotorActuator._clip_effort in
+// their order, each rounded once (no contraction), so that the engine and the torch path
+// agree bit for bit.  Reads only: a world's phase A may run more than once per substep.
+__device__ __forceinline__ float explicit_ctrl(const ActParams& A, int w, int u, int nu, float q,
+                                               float qd) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)w * nu + u;
+  float pt = A.pt[i];
+  const int L = A.ring_len;
+  if (L > 0 && A.max_lag[u] > 0) {
+    // frame `lag` substeps back, the lag clamped to the frames pushed since the reset
+    const int lag = min(A.lag[i], min(A.pushes[i], L));
+    if (lag > 0) pt = A.ring[((size_t)w * L + (L - lag)) * nu + u];
+  }
+  if (A.kind[u] == kActDelayed) return pt;  // a delayed builtin actuator: its ctrl, late
+  // plain operators, which the pragma above keeps apart (the __fmul_rn / __fadd_rn inlines
+  // are compiled under their header's contraction mode and were seen fused into v_fmac)
+  float t = A.kp[i] * (pt - q);
+  t = t + A.kd[i] * (A.vt[i] - qd);
+  t = t + A.ft[i];
+  const float flim = A.flim[i];
+  float lo = -flim, hi = flim;
+  if (A.kind[u] == kActDcMotor) {
+    const float sat = A.sat[i], vc = A.vcorner[i];
+    const float r = act_div(fminf(fmaxf(qd, -vc), vc), A.vlim[i]);
+    hi = fminf(sat * (1.0f - r), flim);    // torque-speed line, then the
+    lo = fmaxf(sat * (-1.0f - r), -flim);  // continuous rating
+  }
+  return fminf(fmaxf(t, lo), hi);
+}
+__device__ __forceinline__ uint32_t act_hash(unsigned long long seed, int w, int group, int draw) {
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)(unsigned)w + 1) +
+                         0xD1B54A32D192ED03ull * (unsigned long long)(unsigned)draw +
+                         0x8CB92BA72F3D8DD7ull * (unsigned long long)group;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;  // splitmix64 finaliser
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return (uint32_t)((z ^ (z >> 31)) >> 32);
+}
+// After an integrated substep: shift actuator u's ring column by one frame, append the
+// substep's position target and draw the next substep's lag, uniform on [min_lag, max_lag]
+// from a counter hash of (seed, world, group, draws) -- the actuators of a group share their
+// draws.  `draws` only ever counts up, so an episode never repeats the last one's sequence.
+__device__ __forceinline__ void act_push(const ActParams& A, int w, int u, int nu) {
+  if (u >= nu || A.kind[u] == kActBuiltin || A.max_lag[u] == 0) return;
+  const int L = A.ring_len;
+  const size_t i = (size_t)w * nu + u;
+  float* r = A.ring + (size_t)w * L * nu + u;
+  for (int k = 0; k + 1 < L; k++) r[(size_t)k * nu] = r[(size_t)(k + 1) * nu];
+  r[(size_t)(L - 1) * nu] = A.pt[i];
+  A.pushes[i] = min(A.pushes[i] + 1, L);
+  const int lo = A.min_lag[u], span = A.max_lag[u] - lo + 1;
+  if (span > 1 && !(A.hold && A.hold[i])) {  // a lag pinned by set_lags(hold) stays
+    const int n = A.draws[i];
+    A.lag[i] = lo + (int)(((unsigned long long)act_hash(A.seed, w, A.group[u], n) * (unsigned)span) >> 32);
+    A.draws[i] = (int)((unsigned)n + 1u);
+  }
+}
 // contact bodies packed in one int (nbody <= 64): b1 | b2 << 8 | root(b1) << 16 | root(b2) << 24
 __device__ __forceinline__ int cb_b1(int v) { return v & 255; }
 __device__ __forceinline__ int cb_b2(int v) { return (v >> 8) & 255; }
@@ -2276,6 +2340,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       const float g = Ar.gear;
       float len = g * S[L.qpos + Ar.qa], vel = g * S[L.qvel + Ar.dof];
       float c = ctrl_u;
+      if (P->act_on) {  // wave-uniform: explicit actuators are bound (mjx_sim_set_actuators)
+        if (P->act.kind[u] != kActBuiltin) {
+          c = explicit_ctrl(P->act, w, u, nu, S[L.qpos + Ar.qa], S[L.qvel + Ar.dof]);
+          if (last) D.ctrl[(size_t)w * nu + u] = c;  // data.ctrl shows the applied torque
+        }
+      }
       if (Ar.ctrllim) c = fminf(fmaxf(c, Ar.cr0), Ar.cr1);
       float f = Ar.gain * c + Ar.b0 + Ar.b1 * len + Ar.b2 * vel;
       if (Ar.forcelim) f = fminf(fmaxf(f, Ar.fr0), Ar.fr1);
@@ -3880,6 +3950,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         }
         if (lane == 0) P->air_time[w] = time;
       }
+      // delayed explicit actuators: this block runs once per world and integrated substep
+      // (phase A may run twice -- the overflow re-solve -- and in a masked forward, so its
+      // read of the ring has no side effect); lane u alone touches actuator u's column
+      if (P->act_on && P->act.ring_len > 0) act_push(P->act, w, lane, nu);
     }
     STAMP(13);
   }

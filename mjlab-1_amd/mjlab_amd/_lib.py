@@ -21,7 +21,7 @@ EXPORTS = ("mjx_last_error", "mjx_abi_version", "mjx_model_desc_size", "mjx_mode
            "mjx_field_is_expanded", "mjx_sim_stats", "mjx_sim_profile", "mjx_sim_spec",
            "mjx_forward_masked", "mjx_sim_track_air_time", "mjx_marker", "mjx_sim_create_ex",
            "mjx_sim_info", "mjx_sim_mass_matrix", "mjx_spec_register", "mjx_launch_counts",
-           "mjx_launch_counts_reset",
+           "mjx_launch_counts_reset", "mjx_sim_set_actuators", "mjx_actuator_desc_size",
            # include/mjx355_task.h (fused velocity-task managers; bound in fused.py)
            "mjx_task_create", "mjx_task_destroy", "mjx_task_action", "mjx_task_substep",
            "mjx_task_post", "mjx_task_reset", "mjx_task_observe", "mjx_task_desc_size",
@@ -85,6 +85,9 @@ def lib() -> ctypes.CDLL:
                                      vp, vp, vp]
   if hasattr(L, "mjx_sim_track_air_time"):
     L.mjx_sim_track_air_time.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int32)] + [vp] * 6
+  if hasattr(L, "mjx_sim_set_actuators"):
+    L.mjx_sim_set_actuators.argtypes = [vp, vp, vp]
+    L.mjx_actuator_desc_size.restype = ctypes.c_size_t
   missing = [n for n in EXPORTS if not hasattr(L, n)]
   if missing and not os.environ.get("MJX355_LIB"):  # MJX355_LIB: A/B against an older build
     raise MjxError(f"{LIB_PATH} lacks {missing}: rebuild it (make -C mjlab-1_amd/csrc)")
@@ -93,7 +96,8 @@ def lib() -> ctypes.CDLL:
       continue
     if name.startswith(("mjx_task_", "mjx_track_")):
       continue  # bound by mjlab_amd.fused / mjlab_amd.fused_tracking
-    if name not in ("mjx_last_error", "mjx_field_name", "mjx_model_desc_size"):
+    if name not in ("mjx_last_error", "mjx_field_name", "mjx_model_desc_size",
+                    "mjx_actuator_desc_size"):
       getattr(L, name).restype = ci
   from ._capi import ABI_VERSION
   if L.mjx_abi_version() != ABI_VERSION:

@@ -9,6 +9,7 @@ damping = 2 * 2.0 * armature * (2*pi*10Hz), effort limits from the motor specs.
 
 from __future__ import annotations
 
+import copy
 import json
 import os
 
@@ -174,7 +175,7 @@ def get_g1_robot_cfg(init: dict | None = None):
   builtin position-actuator groups, soft joint limits at 90 %."""
   from .entity import EntityArticulationInfoCfg, EntityCfg
   return EntityCfg(init_state=_init_state(init or G1_KNEES_BENT), spec_fn=get_g1_spec,
-                   collisions=(G1_FULL_COLLISION,),
+                   collisions=(copy.deepcopy(G1_FULL_COLLISION),),  # a cfg edit stays in its cfg
                    articulation=EntityArticulationInfoCfg(actuators=g1_actuators(),
                                                           soft_joint_pos_limit_factor=0.9))
 
@@ -183,6 +184,6 @@ def get_go1_robot_cfg():
   """`go1_constants.py:140-160` (`get_go1_robot_cfg`)."""
   from .entity import EntityArticulationInfoCfg, EntityCfg
   return EntityCfg(init_state=_init_state(GO1_INIT), spec_fn=get_go1_spec,
-                   collisions=(GO1_FULL_COLLISION,),
+                   collisions=(copy.deepcopy(GO1_FULL_COLLISION),),  # a cfg edit stays in its cfg
                    articulation=EntityArticulationInfoCfg(actuators=go1_actuators(),
                                                           soft_joint_pos_limit_factor=0.9))

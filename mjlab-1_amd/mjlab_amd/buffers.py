@@ -84,7 +84,9 @@ class CircularBuffer:
     if self._frames is not None:
       self._frames.masked_fill_(mask.view(-1, *([1] * (self._frames.dim() - 1))), 0.0)
 
-  def append(self, data: torch.Tensor) -> None:
+  def append(self, data: torch.Tensor, mask: torch.Tensor | None = None) -> None:
+    """`mask` (`[batch]` bool): only these rows take the frame; the others keep their frames
+    and push count (no index list: records into a HIP graph)."""
     if data.shape[0] != self._batch_size:
       raise ValueError(f"Expected batch size {self._batch_size}, got {data.shape[0]}")
     data = data.to(self._device)
@@ -94,8 +96,13 @@ class CircularBuffer:
     new = data.unsqueeze(1)
     shifted = torch.cat([self._frames[:, 1:], new], dim=1)
     fresh = (self._num_pushes == 0).view(-1, *([1] * (shifted.dim() - 1)))
-    self._frames.copy_(torch.where(fresh, new, shifted))
-    self._num_pushes += 1
+    if mask is None:
+      self._frames.copy_(torch.where(fresh, new, shifted))
+      self._num_pushes += 1
+      return
+    rows = mask.view(-1, *([1] * (shifted.dim() - 1)))
+    self._frames.copy_(torch.where(rows, torch.where(fresh, new, shifted), self._frames))
+    self._num_pushes += mask.to(self._num_pushes.dtype)
 
   def __getitem__(self, key: torch.Tensor | int) -> torch.Tensor:
     """Frame `key` steps back per row (0 = newest), the lag clamped to what the row holds."""
@@ -186,16 +193,18 @@ class DelayBuffer:
       drawn = self._draw(0, self.update_period, self.batch_size)
       self._phase_offsets.copy_(torch.where(mask, drawn, self._phase_offsets))
 
-  def append(self, data: torch.Tensor) -> None:
-    self._buffer.append(data)
+  def append(self, data: torch.Tensor, mask: torch.Tensor | None = None) -> None:
+    self._buffer.append(data, mask)
 
-  def compute(self) -> torch.Tensor:
+  def compute(self, mask: torch.Tensor | None = None, hold: torch.Tensor | None = None) -> torch.Tensor:
+    """`mask` (`[batch]` bool): only these rows advance (lag redraw, step count), the others
+    read the frame of the lag they hold.  `hold`: rows that keep their lag through the redraw."""
     if not self.is_initialized:
       raise RuntimeError("Buffer not initialized. Call append() first.")
-    self._update_lags()
+    self._update_lags(mask, hold)
     return self._buffer[self._current_lags]  # __getitem__ clamps to the frames held
 
-  def _update_lags(self) -> None:
+  def _update_lags(self, mask: torch.Tensor | None = None, hold: torch.Tensor | None = None) -> None:
     if self.update_period > 0:
       due = (self._step_count + self._phase_offsets) % self.update_period == 0
     else:
@@ -208,5 +217,9 @@ class DelayBuffer:
       u = torch.rand(self.batch_size, dtype=torch.float32, device=self.device,
                      generator=self.generator)
       due = due & (u >= self.hold_prob)
+    if hold is not None:
+      due = due & ~hold
+    if mask is not None:
+      due = due & mask
     self._current_lags.copy_(torch.where(due, drawn, self._current_lags))
-    self._step_count += 1
+    self._step_count += 1 if mask is None else mask.to(self._step_count.dtype)

@@ -2,8 +2,8 @@
 
 Restates `src/mjlab/entity/entity.py:52-207`: an `EntityCfg` holds a spec factory
 (`spec_fn`, here returning this build's `mjlab_amd.spec.Spec`), the initial state that
-becomes the entity's part of the scene keyframe, the articulation (builtin actuator groups,
-soft joint-limit factor) and the collision edits.  `EntityBuild` is the construction-time
+becomes the entity's part of the scene keyframe, the articulation (builtin actuator groups
+and explicit actuator cfgs of `mjlab_amd.actuator`, soft joint-limit factor) and the collision edits.  `EntityBuild` is the construction-time
 half of the reference's `Entity.__init__` (spec built, fixed base wrapped in a mocap body,
 names resolved); the runtime half (index tensors, `EntityData`) is `scene.Entity`, bound
 after the scene is compiled.
@@ -17,6 +17,8 @@ from typing import Callable
 
 import numpy as np
 
+from .actuator import (ActuatorCfg, DcMotorActuatorCfg, DelayedActuatorCfg,  # noqa: F401
+                       IdealPdActuatorCfg)
 from .compiler.model import (ActuatorSpec, CollisionEdit, EntitySpec, MotorActuatorGroup,
                              PositionActuatorGroup, VelocityActuatorGroup)
 from .spec import Spec, auto_wrap_fixed_base_mocap, mjtJoint
@@ -112,6 +114,11 @@ class EntityBuild:
     acts = [a.to_actuator_spec() for a in self.spec.actuators]
     if cfg.articulation is not None:
       for grp in cfg.articulation.actuators:
+        if isinstance(grp, ActuatorCfg):
+          # an explicit actuator (mjlab_amd.actuator): the model gets the <motor> group it
+          # compiles to, `scene.Entity` builds the runtime object that computes its torque
+          acts.append(grp.compile_group())
+          continue
         if not isinstance(grp, (PositionActuatorGroup, MotorActuatorGroup, VelocityActuatorGroup,
                                 ActuatorSpec)):
           raise TypeError(f"entity '{self.name}': unsupported actuator cfg {type(grp).__name__}")

@@ -195,7 +195,7 @@ class ManagerBasedRlEnv:
     self.reset_time_outs = self.termination_manager.time_outs
     self.reward_buf = self.reward_manager.compute(dt=self.step_dt)
     self._reset_masked(self.reset_buf)
-    self.scene.write_data_to_sim()
+    self.scene.write_data_to_sim(mask=self.reset_buf)
     self.sim.forward(mask=self.reset_buf)
     self.command_manager.compute(dt=self.step_dt)
     if "interval" in self.event_manager.available_modes:

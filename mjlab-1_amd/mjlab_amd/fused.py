@@ -154,6 +154,54 @@ def _ptr(t: torch.Tensor, typ=_FP):
   return ctypes.cast(ctypes.c_void_p(t.data_ptr()), typ)
 
 
+def explicit_actuator_entities(env, robot):
+  """The entities whose explicit actuators (`mjlab_amd.actuator`) a fused step of the action
+  term on `robot` hands to the engine; () when the scene has none.  A fused step runs the
+  `decimation` substeps in one launch, so the laws and the delay have to run in phase A:
+  every actuator of `robot` must then be explicit and of a policy the engine runs."""
+  from .actuator import engine_unsupported
+  ents = [e for e in env.scene.entities.values() if getattr(e, "custom_actuators", ())]
+  if not ents:
+    return ()
+  acts = robot.custom_actuators
+  covered = sorted(c for a in acts for c in a._ctrl_ids_list)
+  _need(covered == list(range(len(robot.indexing.ctrl_ids))),
+        "a mix of builtin and explicit actuators on the action term's entity (engine mode "
+        "needs every one explicit)")
+  for e in ents:
+    for a in e.custom_actuators:
+      why = engine_unsupported(a)
+      _need(why is None, f"explicit actuator of '{e.name}': {why}")
+  return tuple(ents)
+
+
+def bind_explicit_actuators(step, desc):
+  """Engine mode for `step._explicit` (after the descriptor is otherwise complete): the task's
+  `ctrl` becomes the engine's position-target buffer, so the action kernel's store and the
+  reset kernel's clear set the target phase A reads; velocity and effort targets stay zero, as
+  JointPositionAction leaves them.  Returns the binding (None: nothing explicit)."""
+  if not step._explicit:
+    return None
+  sim = step.env.sim
+  try:
+    eng = sim.set_explicit_actuators(step._explicit)
+  except ValueError as e:
+    raise Unsupported(f"explicit actuators: {e}")
+  for ent in step._explicit:  # targets the entity holds now (a step before the first action)
+    eng.write_targets(ent)
+  desc.ctrl = _ptr(eng.position_target)
+  return eng
+
+
+def release_explicit_actuators(step) -> None:
+  """Back to the torch path when the env drops the fused step."""
+  eng, step._engine_act = getattr(step, "_engine_act", None), None
+  sim = step.env.sim
+  if eng is not None and sim.explicit_actuators is eng and getattr(sim, "_sim", None) is not None \
+      and sim._sim.value:
+    sim.clear_explicit_actuators()
+
+
 def _noise(cfg):
   n = cfg.noise
   if n is None:
@@ -299,7 +347,12 @@ class FusedVelocityStep:
     self._keep = []
     self._task = None
     self._desc = self._make_desc(env)
-    self.upload()
+    self._engine_act = bind_explicit_actuators(self, self._desc)
+    try:
+      self.upload()
+    except Exception:
+      release_explicit_actuators(self)  # the env falls back in torch mode
+      raise
     self._engine_air = self._track_air_time()
 
   # ------------------------------------------------------------------ descriptor
@@ -425,6 +478,7 @@ class FusedVelocityStep:
     _need(isinstance(aterm, mdp.JointPositionAction), "JointPositionAction only")
     robot = aterm._asset
     self._robot = robot
+    self._explicit = explicit_actuator_entities(env, robot)
     rdata = robot.data
     _need(float(rdata.encoder_bias.abs().max()) == 0.0 if rdata.encoder_bias.numel() else True,
           "encoder bias")
@@ -693,6 +747,7 @@ class FusedVelocityStep:
       # the observation history / delay state goes back to the manager's buffers
       self._obs_hist.hand_back(self.obs)
       self._obs_hist = None
+    release_explicit_actuators(self)
     if not getattr(self, "_engine_air", False):
       return
     sim = self.env.sim
@@ -769,6 +824,8 @@ class FusedVelocityStep:
     mask = ctypes.c_void_p(self.reset_buf.data_ptr())
     check(lib().mjx_reset(sim._sim, mask, stream))
     self._ok(L.mjx_task_reset(self._task, stream))
+    if self._engine_act is not None:  # delay history of the reset envs: cleared, one frame
+      self._engine_act.reset_masked(self.reset_buf)
     check(lib().mjx_forward_masked(sim._sim, mask, stream))
     self._ok(L.mjx_task_observe(self._task, stream))
     tm = env.termination_manager

@@ -25,7 +25,8 @@ from . import mdp
 from . import tracking as trk
 from ._lib import MjxError, check, lib
 from .fused import (MAXJ, MAXT, FusedObsHistory, ObsState, Unsupported, _f2, _f62, _FP, _I64, _need,
-                    _noise, _ptr, _range6, _U8, _U64)
+                    _noise, _ptr, _range6, _U8, _U64, bind_explicit_actuators,
+                    explicit_actuator_entities, release_explicit_actuators)
 
 MAXB, NMETRIC = 32, 13
 _I32 = ctypes.c_int
@@ -130,7 +131,12 @@ class FusedTrackingStep:
     self._keep = []
     self._task = None
     self._desc = self._make_desc(env)
-    self.upload()
+    self._engine_act = bind_explicit_actuators(self, self._desc)
+    try:
+      self.upload()
+    except Exception:
+      release_explicit_actuators(self)  # the env falls back in torch mode
+      raise
 
   # ------------------------------------------------------------------ descriptor
   def _make_desc(self, env):
@@ -156,6 +162,7 @@ class FusedTrackingStep:
     _need(isinstance(aterm, mdp.JointPositionAction), "JointPositionAction only")
     robot = aterm._asset
     _need(robot is c.robot, "command and action on one entity")
+    self._explicit = explicit_actuator_entities(env, robot)
     rdata = robot.data
     idx = robot.indexing
     nj = len(idx.joint_q_adr)
@@ -412,6 +419,7 @@ class FusedTrackingStep:
     if getattr(self, "_obs_hist", None) is not None:
       self._obs_hist.hand_back(self.obs)
       self._obs_hist = None
+    release_explicit_actuators(self)
 
   def __del__(self):
     try:
@@ -441,6 +449,8 @@ class FusedTrackingStep:
     mask = ctypes.c_void_p(self.reset_buf.data_ptr())
     check(lib().mjx_reset(sim._sim, mask, stream))
     self._ok(L.mjx_track_reset(self._task, stream))
+    if self._engine_act is not None:  # delay history of the reset envs: cleared, one frame
+      self._engine_act.reset_masked(self.reset_buf)
     check(lib().mjx_forward_masked(sim._sim, mask, stream))
     self._ok(L.mjx_track_observe(self._task, stream))
     tm = env.termination_manager

@@ -284,7 +284,8 @@ class Entity:
   """One attached MJCF entity (prefix '<name>/') with builtin position actuators."""
 
   def __init__(self, name: str, mj_model, soft_joint_pos_limit_factor: float = 0.9,
-               init_lin_vel=(0.0, 0.0, 0.0), init_ang_vel=(0.0, 0.0, 0.0)):
+               init_lin_vel=(0.0, 0.0, 0.0), init_ang_vel=(0.0, 0.0, 0.0),
+               actuator_cfgs=(), num_spec_actuators: int = 0):
     self.name = name
     self._m = mj_model
     self._prefix = f"{name}/"
@@ -309,6 +310,38 @@ class Entity:
     self.is_actuated = len(self._act_gid) > 0
     # actuator -> entity-local joint index (BuiltinActuatorGroup, actuator/builtin_group.py)
     self._act_joint_local = [self._jnt_gid.index(int(m.actuator_trnid[a])) for a in self._act_gid]
+    self._custom_actuators = self._build_custom_actuators(actuator_cfgs, num_spec_actuators)
+    # set by Simulation.set_explicit_actuators: the engine's phase A evaluates the explicit
+    # actuators, write_data_to_sim copies their targets only
+    self._engine_actuators = None
+
+  def _build_custom_actuators(self, cfgs, first: int) -> list:
+    """The runtime objects of the explicit actuator cfgs (`entity.py:155-168`).  The entity's
+    actuators are the spec's own, then one per matched joint of every articulation group in
+    cfg order (`EntityBuild.entity_spec`): that order gives each group its ctrl ids."""
+    from .actuator import ActuatorCfg
+    from .compiler.model import ActuatorSpec
+    out, at = [], int(first)
+    for cfg in cfgs:
+      if isinstance(cfg, ActuatorSpec):
+        at += 1
+        continue
+      names = [n for n in self.joint_names if any(re.fullmatch(e, n) for e in cfg.joint_names_expr)]
+      if isinstance(cfg, ActuatorCfg):
+        ctrl = list(range(at, at + len(names)))
+        if [self.actuator_names[c] for c in ctrl if c < len(self.actuator_names)] != names:
+          raise ValueError(f"entity '{self.name}': actuators of {cfg.joint_names_expr} are not "
+                           f"where the cfg order puts them ({self.actuator_names})")
+        act = cfg.build(self, [self.joint_names.index(n) for n in names], names)
+        act._ctrl_ids_list = ctrl
+        out.append(act)
+      at += len(names)
+    return out
+
+  @property
+  def custom_actuators(self) -> tuple:
+    """The explicit actuators (`mjlab_amd.actuator`), in cfg order."""
+    return tuple(self._custom_actuators)
 
   # name resolution (natural order)
   def find_joints(self, keys, joint_subset=None, preserve_order=False):
@@ -366,6 +399,10 @@ class Entity:
     soft = torch.stack([mean - half, mean + half], dim=-1)
     self._data = EntityData(self.indexing, data, model, dev, n, drs, djp, djv, rng, soft)
     self._act_joint_local_t = t(self._act_joint_local)
+    for act in self._custom_actuators:
+      act.initialize(mj_model, model, data, dev)
+    # the model's ctrl columns of each explicit actuator (the masked write keeps their rows)
+    self._custom_ctrl_cols = [self.indexing.ctrl_ids[act.ctrl_ids] for act in self._custom_actuators]
 
   @property
   def data(self) -> EntityData:
@@ -412,20 +449,52 @@ class Entity:
     j = slice(None) if joint_ids is None else joint_ids
     self._data.joint_effort_target[e, j] = effort
 
-  def write_data_to_sim(self):
-    """BuiltinActuatorGroup.apply_controls: ctrl[:, ctrl_ids] = target[:, joint_ids]."""
+  def write_data_to_sim(self, mask=None):
+    """BuiltinActuatorGroup.apply_controls: ctrl[:, ctrl_ids] = target[:, joint_ids]; then
+    every explicit actuator's torque from the targets and the joint state
+    (`entity.py:815-825`).  `mask`: the rows whose explicit actuators are evaluated -- a delayed
+    actuator steps only those (the sync-free env's post-reset write passes its reset mask;
+    see `DelayedActuator.compute`)."""
+    if self._engine_actuators is not None:
+      self._engine_actuators.write_targets(self)
+      return
+    held = None
+    if mask is not None:  # the explicit torques the other rows keep (these columns only)
+      held = [self._data.data.ctrl[:, cols] for cols in self._custom_ctrl_cols]
     if self.is_actuated:
       self._data.data.ctrl[:, self.indexing.ctrl_ids] = \
         self._data.joint_pos_target[:, self._act_joint_local_t]
+    if not self._custom_actuators:
+      return
+    from .actuator import ActuatorCmd, DelayedActuator
+    d = self._data
+    for k, act in enumerate(self._custom_actuators):
+      j = act.joint_ids
+      cmd = ActuatorCmd(position_target=d.joint_pos_target[:, j],
+                        velocity_target=d.joint_vel_target[:, j],
+                        effort_target=d.joint_effort_target[:, j],
+                        joint_pos=d.joint_pos[:, j], joint_vel=d.joint_vel[:, j])
+      if mask is None:
+        d.write_ctrl(act.compute(cmd), act.ctrl_ids)
+        continue
+      # masked: the other rows keep their ctrl (as the engine's masked forward leaves it)
+      m = mask.bool()
+      ctrl = act.compute(cmd, mask=m) if isinstance(act, DelayedActuator) else act.compute(cmd)
+      d.data.ctrl[:, self._custom_ctrl_cols[k]] = torch.where(m.unsqueeze(1), ctrl, held[k])
 
   def update(self, dt: float):
-    pass
+    for act in self._custom_actuators:
+      act.update(dt)
 
   def reset(self, env_ids=None):
     self._data.clear_state(env_ids)
+    for act in self._custom_actuators:
+      act.reset(env_ids)
 
   def reset_masked(self, mask):
     self._data.clear_state_masked(mask)
+    for act in self._custom_actuators:
+      act.reset_masked(mask)
 
 
 class BuiltinSensor:
@@ -763,9 +832,12 @@ class Scene:
     for name, b in self._builds.items():
       art = b.cfg.articulation
       init = b.cfg.init_state
+      spec = getattr(b, "spec", None)
       self._entities[name] = Entity(
         name, mj_model, soft_joint_pos_limit_factor=art.soft_joint_pos_limit_factor if art else 1.0,
-        init_lin_vel=init.lin_vel, init_ang_vel=init.ang_vel)
+        init_lin_vel=init.lin_vel, init_ang_vel=init.ang_vel,
+        actuator_cfgs=tuple(art.actuators) if art else (),
+        num_spec_actuators=len(spec.actuators) if spec is not None else 0)
     self._sensors = {}
     names = mj_model.names["sensor"]
     adr, dim = mj_model.sensor_adr, mj_model.sensor_dim
@@ -853,6 +925,6 @@ class Scene:
     for s in self._sensors.values():
       s.update(dt)
 
-  def write_data_to_sim(self):
+  def write_data_to_sim(self, mask=None):
     for e in self._entities.values():
-      e.write_data_to_sim()
+      e.write_data_to_sim(mask)

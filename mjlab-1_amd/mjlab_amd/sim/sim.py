@@ -440,6 +440,42 @@ class Simulation:
     check(lib().mjx_reset(self._sim, ctypes.c_void_p(m.data_ptr()),
                           _stream_handle(self._torch_device)))
 
+  def set_explicit_actuators(self, entities, seed: int | None = None):
+    """Engine mode of the explicit actuators (`mjlab_amd.actuator`) of `entities` (scene
+    entities, e.g. `scene.entities.values()`): the step kernels' phase A evaluates their laws
+    at every substep's own joint state, so `step(n)` equals n rounds of the torch path's
+    `write_data_to_sim()` + `step(1)`, and `Entity.write_data_to_sim` copies targets only.
+    Raises ValueError for an actuator the engine cannot run (`actuator.engine_unsupported`).
+    `seed` seeds the lag draws of delayed actuators.  Returns the binding."""
+    from ..actuator import ActuatorDesc, EngineActuators
+    L = lib()
+    if L.mjx_actuator_desc_size() != ctypes.sizeof(ActuatorDesc):
+      raise MjxError("mjxActuatorDesc layout mismatch between include/mjx355.h and actuator.py")
+    self.clear_explicit_actuators()
+    eng = EngineActuators(self, entities, seed)
+    try:
+      check(L.mjx_sim_set_actuators(self._sim, ctypes.addressof(eng.desc),
+                                    _stream_handle(self._torch_device)))
+    except MjxError:
+      eng.release()
+      raise
+    self._explicit_actuators = eng
+    return eng
+
+  def clear_explicit_actuators(self) -> None:
+    """Back to the torch path: `Entity.write_data_to_sim` computes the torques again."""
+    eng = getattr(self, "_explicit_actuators", None)
+    if eng is None:
+      return
+    check(lib().mjx_sim_set_actuators(self._sim, None, _stream_handle(self._torch_device)))
+    eng.release()
+    self._explicit_actuators = None
+
+  @property
+  def explicit_actuators(self):
+    """The engine-mode binding (`actuator.EngineActuators`), None in torch mode."""
+    return getattr(self, "_explicit_actuators", None)
+
   def step(self, nsubstep: int = 1) -> None:
     """One mj_step for every world (or `nsubstep` steps fused in one launch)."""
     with self.nan_guard.watch(self.data):
