@@ -967,8 +967,10 @@ __device__ __forceinline__ int hfield_sphere(const ConOut& co, int key, int g1, 
   const V3 loc = mulTv(F.R, center - F.p);
   const float sx = hsize[0], sy = hsize[1], sz = hsize[2];
   const float dx = 2 * sx / (nc - 1), dy = 2 * sy / (nr - 1);
-  int c0 = (int)floorf((loc.x - r + sx) / dx), c1 = (int)floorf((loc.x + r + sx) / dx);
-  int r0 = (int)floorf((loc.y - r + sy) / dy), r1 = (int)floorf((loc.y + r + sy) / dy);
+  // cells under the sphere grown by the margin: a surface point within the margin lies there
+  const float rm = r + margin;
+  int c0 = (int)floorf((loc.x - rm + sx) / dx), c1 = (int)floorf((loc.x + rm + sx) / dx);
+  int r0 = (int)floorf((loc.y - rm + sy) / dy), r1 = (int)floorf((loc.y + rm + sy) / dy);
   if (c1 < 0 || r1 < 0 || c0 > nc - 2 || r0 > nr - 2) return 0;
   c0 = max(c0, 0); r0 = max(r0, 0);
   c1 = min(c1, nc - 2); r1 = min(r1, nr - 2);
@@ -1014,8 +1016,14 @@ __device__ __forceinline__ int hfield_sphere(const ConOut& co, int key, int g1, 
         }
         const V3 diff = loc - q;
         float dist = norm(diff);
+        // below the triangle's plane and inside its prism (its footprint in x, y): the
+        // plane's normal and depth; below the plane of a triangle the centre is not under
+        // (a neighbour past a ridge): the closest point, as above the plane
+        const float ux = loc.x - x0, uy = loc.y - y0;
+        const bool under = sd < 0 && ux >= 0 && ux <= dx && uy >= 0 && uy <= dy &&
+                           (k == 0 ? uy * dx <= ux * dy : uy * dx >= ux * dy);
         V3 nn;
-        if (dist < MINVAL || sd < 0) { nn = n; dist = sd; }
+        if (dist < MINVAL || under) { nn = n; dist = sd; }
         else { nn = diff * (1.0f / dist); }
         dist -= r;
         if (dist < best) { best = dist; bestn = nn; found = true; }

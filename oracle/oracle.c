@@ -565,8 +565,10 @@ static int col_hfield_sphere(const mjxModelDesc* m, orcData* d, int g1, int g2,
   int nr = m->hfield_nrow[h], nc = m->hfield_ncol[h];
   double sx = m->hfield_size[4 * h], sy = m->hfield_size[4 * h + 1];
   double dx = 2 * sx / (nc - 1), dy = 2 * sy / (nr - 1);
-  int c0 = (int)floor((loc[0] - r + sx) / dx), c1 = (int)floor((loc[0] + r + sx) / dx);
-  int r0 = (int)floor((loc[1] - r + sy) / dy), r1 = (int)floor((loc[1] + r + sy) / dy);
+  /* cells under the sphere grown by the margin: a surface point within the margin lies there */
+  const double rm = r + margin;
+  int c0 = (int)floor((loc[0] - rm + sx) / dx), c1 = (int)floor((loc[0] + rm + sx) / dx);
+  int r0 = (int)floor((loc[1] - rm + sy) / dy), r1 = (int)floor((loc[1] + rm + sy) / dy);
   if (c1 < 0 || r1 < 0 || c0 > nc - 2 || r0 > nr - 2) return 0;
   c0 = c0 < 0 ? 0 : c0; r0 = r0 < 0 ? 0 : r0;
   c1 = c1 > nc - 2 ? nc - 2 : c1; r1 = r1 > nr - 2 ? nr - 2 : r1;
@@ -621,9 +623,15 @@ static int col_hfield_sphere(const mjxModelDesc* m, orcData* d, int g1, int g2,
         double diff[3];
         v3_sub(diff, loc, q);
         double dist = v3_norm(diff);
+        /* below the triangle's plane and inside its prism (its footprint in x, y): the
+         * plane's normal and depth; below the plane of a triangle the centre is not under
+         * (a neighbour past a ridge): the closest point, as above the plane */
+        const double ux = loc[0] - x0, uy = loc[1] - y0;
+        const int under = sd < 0 && ux >= 0 && ux <= dx && uy >= 0 && uy <= dy &&
+                          (k == 0 ? uy * dx <= ux * dy : uy * dx >= ux * dy);
         double nn[3];
-        if (dist < MINVAL || sd < 0) { v3_copy(nn, n); dist = sd; }
-        else { v3_scl(nn, diff, 1.0 / dist); if (sd < 0) dist = -dist; }
+        if (dist < MINVAL || under) { v3_copy(nn, n); dist = sd; }
+        else v3_scl(nn, diff, 1.0 / dist);
         dist -= r;
         if (dist < best) { best = dist; v3_copy(bestp, q); v3_copy(bestn, nn); found = 1; }
       }

@@ -23,6 +23,7 @@ from mjlab_amd import terrains as T
 from mjlab_amd.compiler.mjcf import parse_mjcf_string
 from mjlab_amd.compiler.model import BoxSpec, EntitySpec, compile_scene
 from mjlab_amd.scenes import load_scene
+from narrowphase_ref import segment_box_distance as _exact_capsule_box
 
 
 def _top_at(boxes, x, y):
@@ -249,31 +250,6 @@ def test_box_edge_across_a_box_edge():
   ex = np.array([np.cos(0.3), 0.0, -np.sin(0.3)])                 # moving edge direction
   n = c[6:9]
   assert abs(n[1]) < 1e-9 and abs(n @ ex) < 1e-9 and n[2] > 0.5   # normal to both edges
-
-
-def _exact_capsule_box(c, a, hl, s):
-  """min over the segment c + t a (|t| <= hl) of the box signed distance (box frame, half
-  sizes s), fp64: dense samples, then golden refinement in the best bracket; returns
-  (distance, t) -- an oracle-independent restatement of what MuJoCo's first capsule-box
-  contact reports (the sphere at the segment point closest to the box)."""
-  def sd(t):
-    q = c[None, :] + np.atleast_1d(t)[:, None] * a[None, :]
-    d = np.abs(q) - s
-    out = np.linalg.norm(np.maximum(d, 0.0), axis=1) + np.minimum(d.max(axis=1), 0.0)
-    return out
-  ts = np.linspace(-hl, hl, 4001)
-  v = sd(ts)
-  k = int(np.argmin(v))
-  lo, hi = ts[max(k - 1, 0)], ts[min(k + 1, len(ts) - 1)]
-  for _ in range(80):
-    m1, m2 = lo + (hi - lo) * 0.382, lo + (hi - lo) * 0.618
-    if sd(m1)[0] <= sd(m2)[0]:
-      hi = m2
-    else:
-      lo = m1
-  t = 0.5 * (lo + hi)
-  cand = [(float(sd(t)[0]), t), (float(v[k]), ts[k])]
-  return min(cand)
 
 
 def test_capsule_box_deepest_contact_is_the_exact_distance():

@@ -124,7 +124,9 @@ def test_oracle_row_counts(oracle):
   assert nc.max() <= 48 and not any(r["overflow"] for r in oracle["g1"][1])
   assert ((ne > SMALL[1]) | (nc > SMALL[0])).sum() >= 27 and (ne > SMALL[1]).sum() >= 27
   nc, ne = _counts(oracle["hfield"][1])
-  assert ((ne <= CLASS_CAP).sum(), (ne == 0).sum(), (ne > CLASS_CAP).sum(), ne.max()) == (16, 8, 48, 136)
+  # (10 worlds without a row: in two of them the hfield narrowphase used to put a foot sphere
+  # 3.5 cm above the surface 2 cm into the extended plane of a triangle past a ridge)
+  assert ((ne <= CLASS_CAP).sum(), (ne == 0).sum(), (ne > CLASS_CAP).sum(), ne.max()) == (16, 10, 48, 136)
   assert nc.max() <= 34 and not any(r["overflow"] for r in oracle["hfield"][1])
   nc, ne = _counts(oracle["go1"][1])
   assert (ne.min(), ne.max()) == (4, 32) and nc.max() <= 8
