@@ -308,63 +308,72 @@ __global__ __launch_bounds__(64 * kPostEnvs) void k_post(const mjxTrackDesc* __r
 // counts of the masked envs' current bins (overwriting the current counts when any failed),
 // sampling probabilities (uniform floor, kernel smoothing with right replicate padding),
 // their CDF and the sampling metrics; `ema` then applies _adaptive_update (:301-307).
+// The reference computes all of this inside _resample_command, so only when some env of
+// `mask` resamples: with an empty mask the CDF and the three sampling metrics keep their
+// values (the failure counts move with every EMA, the logged metrics do not), "uniform"
+// writes its fixed metrics on a resample only and "start" never writes any.
 constexpr int kBinThreads = 256;
 __global__ __launch_bounds__(kBinThreads) void k_bins(const mjxTrackDesc* __restrict__ T,
                                                      const uint8_t* __restrict__ mask, int ema) {
   const mjxTrackDesc& t = *T;
   __shared__ float cnt[MJX_TRACK_MAX_BINS];
   __shared__ float pr[MJX_TRACK_MAX_BINS];
-  __shared__ int anyfail;
+  __shared__ int anyfail, anymask;
   const int nbin = t.bin_count, tid = threadIdx.x;
   float* cdf = t.sampling;
-  if (t.sampling_mode != 2) {  // start / uniform: fixed metrics (commands.py:302-307)
-    if (tid == 0) {
-      cdf[nbin + 0] = 1.f;
-      cdf[nbin + 1] = 1.f / (float)nbin;
-      cdf[nbin + 2] = 0.5f;
-    }
-    return;
-  }
+  if (t.sampling_mode == 0) return;
   for (int i = tid; i < nbin; i += kBinThreads) cnt[i] = 0.f;
-  if (tid == 0) anyfail = 0;
+  if (tid == 0) anyfail = anymask = 0;
   __syncthreads();
   for (int e = tid; e < t.nworld; e += kBinThreads) {
-    if (!mask[e] || !t.terminated[e]) continue;
+    if (!mask[e]) continue;
+    anymask = 1;
+    if (t.sampling_mode != 2 || !t.terminated[e]) continue;
     int64_t b = (t.time_steps[e] * nbin) / (t.nframe > 1 ? t.nframe : 1);
     b = b < 0 ? 0 : (b >= nbin ? nbin - 1 : b);
     atomicAdd(&cnt[b], 1.f);
     anyfail = 1;
   }
   __syncthreads();
-  if (anyfail)
-    for (int i = tid; i < nbin; i += kBinThreads) t.current_bin_failed[i] = cnt[i];
-  for (int i = tid; i < nbin; i += kBinThreads) {
-    float v = 0.f;
-    for (int k = 0; k < t.kernel_size; k++) {
-      const int j = min(i + k, nbin - 1);
-      v += t.kernel[k] * (t.bin_failed_count[j] + t.uniform_ratio / (float)nbin);
+  if (t.sampling_mode != 2) {  // uniform: fixed metrics (commands.py:302-307)
+    if (anymask && tid == 0) {
+      cdf[nbin + 0] = 1.f;
+      cdf[nbin + 1] = 1.f / (float)nbin;
+      cdf[nbin + 2] = 0.5f;
     }
-    pr[i] = v;
+    return;
   }
-  __syncthreads();
-  if (tid == 0) {  // serial over a few bins: normalise, cdf, entropy, argmax
-    float s = 0.f;
-    for (int i = 0; i < nbin; i++) s += pr[i];
-    float c = 0.f, h = 0.f, pmax = -1.f;
-    int imax = 0;
-    for (int i = 0; i < nbin; i++) {
-      const float p = pr[i] / s;
-      c += p;
-      cdf[i] = c;
-      h -= p * logf(p + 1e-12f);
-      if (p > pmax) { pmax = p; imax = i; }
+  if (anymask) {  // block-uniform
+    if (anyfail)
+      for (int i = tid; i < nbin; i += kBinThreads) t.current_bin_failed[i] = cnt[i];
+    for (int i = tid; i < nbin; i += kBinThreads) {
+      float v = 0.f;
+      for (int k = 0; k < t.kernel_size; k++) {
+        const int j = min(i + k, nbin - 1);
+        v += t.kernel[k] * (t.bin_failed_count[j] + t.uniform_ratio / (float)nbin);
+      }
+      pr[i] = v;
     }
-    cdf[nbin - 1] = 1.f;
-    cdf[nbin + 0] = h / logf((float)nbin);
-    cdf[nbin + 1] = pmax;
-    cdf[nbin + 2] = (float)imax / (float)nbin;
+    __syncthreads();
+    if (tid == 0) {  // serial over a few bins: normalise, cdf, entropy, argmax
+      float s = 0.f;
+      for (int i = 0; i < nbin; i++) s += pr[i];
+      float c = 0.f, h = 0.f, pmax = -1.f;
+      int imax = 0;
+      for (int i = 0; i < nbin; i++) {
+        const float p = pr[i] / s;
+        c += p;
+        cdf[i] = c;
+        h -= p * logf(p + 1e-12f);
+        if (p > pmax) { pmax = p; imax = i; }
+      }
+      cdf[nbin - 1] = 1.f;
+      cdf[nbin + 0] = h / logf((float)nbin);
+      cdf[nbin + 1] = pmax;
+      cdf[nbin + 2] = (float)imax / (float)nbin;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   if (ema)
     for (int i = tid; i < nbin; i += kBinThreads) {
       t.bin_failed_count[i] = t.bin_failed_count[i] * (1.f - t.adaptive_alpha) +

@@ -996,6 +996,8 @@ struct mjxTask_ {
   // an observe folds the first's with a k_accum launch of its own)
   int pending_nblock = 0;
   int ncu = 256;  // compute units of the device the task was created on
+  // MJX355_TASK_POST_FORM, read at create: 0 = by batch size (below), 1 = k_post<1>, 8 = k_post<8>
+  int post_form = 0;
 };
 
 static thread_local std::string g_task_err;
@@ -1174,6 +1176,14 @@ int mjx_task_create(const mjxTaskDesc* desc, mjxTask** out) {
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
       t->ncu = ncu;
   }
+  if (const char* form = getenv("MJX355_TASK_POST_FORM")) {
+    const int v = atoi(form);
+    if (v != 0 && v != 1 && v != 8) {
+      mjx_task_destroy(t);
+      return task_fail("mjx_task_create: MJX355_TASK_POST_FORM must be 0, 1 or 8");
+    }
+    t->post_form = v;
+  }
   if (hipMemcpy(t->dev, &t->host, sizeof(mjxTaskDesc), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(t->acc, 0, sizeof(mjxt::Acc)) != hipSuccess) {
     delete t;
@@ -1217,7 +1227,7 @@ int mjx_task_post(mjxTask* t, void* stream) {
   if (t->pending_nblock > 0)  // a post without an observe since: fold its partials first
     hipLaunchKernelGGL(mjxt::k_accum, dim3(1), dim3(128 * mjxt::kAccChunks), 0, (hipStream_t)stream,
                        t->part, t->pending_nblock, t->acc);
-  if (nblock > t->ncu)
+  if (t->post_form ? t->post_form == 8 : nblock > t->ncu)
     hipLaunchKernelGGL(mjxt::k_post<8>, dim3(nblock), dim3(64 * mjxt::kPostEnvs), 0, (hipStream_t)stream,
                        t->dev, t->part);
   else

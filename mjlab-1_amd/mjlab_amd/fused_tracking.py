@@ -239,6 +239,9 @@ class FusedTrackingStep:
       self._metrics[k].copy_(c.metrics[name])
       c.metrics[name] = self._metrics[k]
     d.metrics = _ptr(self._metrics)
+    # the kernels keep the sampling metrics in the scratch tail and copy them to every env on
+    # each resample launch: continue from the manager's values (the same on every env)
+    self._sampling[d.bin_count:d.bin_count + 3] = self._metrics[10:13, 0]
     d.time_left, d.command_counter = _ptr(c.time_left), _ptr(c.command_counter, _I64)
     self._cmd = c
     # sensors

@@ -320,12 +320,22 @@ class MotionCommand(CommandTerm):
     p = torch.nn.functional.conv1d(p, self.kernel.view(1, 1, -1)).view(-1)
     return p / p.sum()
 
-  def _sampling_metrics(self, p):
+  def _sampling_metrics(self, p, when=None):
+    """The three sampling metrics of every env; `when` (a device bool scalar of the
+    sync-free path) keeps the old values where it is false: the reference writes them
+    inside _resample_command, so only when some env resamples."""
     H = -(p * (p + 1e-12).log()).sum()
     pmax, imax = p.max(dim=0)
-    self.metrics["sampling_entropy"].fill_(0.0).add_(H / math.log(self.bin_count))
-    self.metrics["sampling_top1_prob"].fill_(0.0).add_(pmax)
-    self.metrics["sampling_top1_bin"].fill_(0.0).add_(imax.float() / self.bin_count)
+    self._set_sampling_metrics(H / math.log(self.bin_count), pmax, imax.float() / self.bin_count,
+                               when)
+
+  def _set_sampling_metrics(self, entropy, top1_prob, top1_bin, when=None):
+    for name, v in (("sampling_entropy", entropy), ("sampling_top1_prob", top1_prob),
+                    ("sampling_top1_bin", top1_bin)):
+      m = self.metrics[name]
+      # a device fill, not a host-to-device copy: this runs under graph capture
+      v = v.to(m.dtype).expand_as(m) if isinstance(v, torch.Tensor) else torch.full_like(m, v)
+      m.copy_(v if when is None else torch.where(when, v, m))
 
   def _current_bins(self):
     return torch.clamp((self.time_steps * self.bin_count) // max(self.motion.time_step_total, 1),
@@ -353,14 +363,12 @@ class MotionCommand(CommandTerm):
     fresh = ((bins + torch.rand(self.num_envs, device=self.device)) / self.bin_count
              * (self.motion.time_step_total - 1)).long()
     self.time_steps.copy_(torch.where(mask, fresh, self.time_steps))
-    self._sampling_metrics(p)
+    self._sampling_metrics(p, when=mask.any())
 
   def _uniform_sampling(self, env_ids):
     self.time_steps[env_ids] = torch.randint(0, self.motion.time_step_total, (len(env_ids),),
                                              device=self.device)
-    self.metrics["sampling_entropy"].fill_(1.0)
-    self.metrics["sampling_top1_prob"].fill_(1.0 / self.bin_count)
-    self.metrics["sampling_top1_bin"].fill_(0.5)
+    self._set_sampling_metrics(1.0, 1.0 / self.bin_count, 0.5)
 
   # ------------------------------------------------------------------ reference-state init
   def _reference_state(self, n):
@@ -407,9 +415,7 @@ class MotionCommand(CommandTerm):
     elif mode == "uniform":
       fresh = torch.randint(0, self.motion.time_step_total, (self.num_envs,), device=self.device)
       self.time_steps.copy_(torch.where(mask, fresh, self.time_steps))
-      self.metrics["sampling_entropy"].fill_(1.0)
-      self.metrics["sampling_top1_prob"].fill_(1.0 / self.bin_count)
-      self.metrics["sampling_top1_bin"].fill_(0.5)
+      self._set_sampling_metrics(1.0, 1.0 / self.bin_count, 0.5, when=mask.any())
     else:
       self._adaptive_sampling_masked(mask)
     n = self.num_envs

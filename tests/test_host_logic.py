@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import fp64_terms as F64
 from mjlab_amd import mdp
 from mjlab_amd.managers import resolve_matching_names, resolve_matching_names_values
 from mjlab_amd.math_utils import (matrix_from_quat, quat_apply, quat_apply_inverse,
@@ -87,8 +88,7 @@ def _np(env, *path):
   return x.numpy().astype(np.float64)
 
 
-def _active(c, thr):
-  return ((np.linalg.norm(c[:, :2], axis=1) + np.abs(c[:, 2])) > thr).astype(np.float64)
+_active = F64.command_active  # the shared fp64 restatements (fp64_terms.py)
 
 
 def test_track_velocity_terms(env):
@@ -96,10 +96,10 @@ def test_track_velocity_terms(env):
   c = env.command_manager.get_command("t").numpy().astype(np.float64)
   v = _np(env, "scene", "robot", "data", "root_link_lin_vel_b")
   w = _np(env, "scene", "robot", "data", "root_link_ang_vel_b")
-  e_lin = np.sum((c[:, :2] - v[:, :2]) ** 2, 1) + v[:, 2] ** 2
-  e_ang = (c[:, 2] - w[:, 2]) ** 2 + np.sum(w[:, :2] ** 2, 1)
-  np.testing.assert_allclose(mdp.track_linear_velocity(env, 0.5, "t").numpy(), np.exp(-e_lin / 0.25), rtol=1e-5, atol=1e-12)
-  np.testing.assert_allclose(mdp.track_angular_velocity(env, 0.5 ** 0.5, "t").numpy(), np.exp(-e_ang / 0.5), rtol=1e-5, atol=1e-12)
+  np.testing.assert_allclose(mdp.track_linear_velocity(env, 0.5, "t").numpy(),
+                             F64.track_linear_velocity(c, v, 0.5), rtol=1e-5, atol=1e-12)
+  np.testing.assert_allclose(mdp.track_angular_velocity(env, 0.5 ** 0.5, "t").numpy(),
+                             F64.track_angular_velocity(c, w, 0.5 ** 0.5), rtol=1e-5, atol=1e-12)
 
 
 def test_flat_orientation_body_and_root(env):
@@ -108,10 +108,11 @@ def test_flat_orientation_body_and_root(env):
   gb = np.array([quat_apply_inverse(_t(qq[None]), _t([0, 0, -1]))[0].numpy() for qq in q])
   std2 = 0.2
   out = mdp.flat_orientation(env, std2 ** 0.5, cfg(body_ids=[3])).numpy()
-  np.testing.assert_allclose(out, np.exp(-np.sum(gb[:, :2] ** 2, 1) / std2), rtol=1e-5)
+  np.testing.assert_allclose(out, F64.flat_orientation(gb, std2 ** 0.5), rtol=1e-5)
+  np.testing.assert_allclose(gb, F64.projected_gravity(q), atol=1e-6)
   g = _np(env, "scene", "robot", "data", "projected_gravity_b")
   out = mdp.flat_orientation(env, std2 ** 0.5, cfg(body_ids=[])).numpy()
-  np.testing.assert_allclose(out, np.exp(-np.sum(g[:, :2] ** 2, 1) / std2), rtol=1e-5)
+  np.testing.assert_allclose(out, F64.flat_orientation(g, std2 ** 0.5), rtol=1e-5)
 
 
 def test_penalties(env):
@@ -126,10 +127,10 @@ def test_penalties(env):
   np.testing.assert_allclose(mdp.angular_momentum_penalty(env, "angmom").numpy(), np.sum(h ** 2, 1), rtol=1e-5)
   assert env.extras["log"]["Metrics/angular_momentum_mean"] == pytest.approx(np.mean(np.linalg.norm(h, axis=1)), rel=1e-5)
   a, pa = env.action_manager.action.numpy(), env.action_manager.prev_action.numpy()
-  np.testing.assert_allclose(mdp.action_rate_l2(env).numpy(), np.sum((a - pa) ** 2, 1), rtol=1e-5)
+  np.testing.assert_allclose(mdp.action_rate_l2(env).numpy(), F64.action_rate_l2(a, pa), rtol=1e-5)
   q = _np(env, "scene", "robot", "data", "joint_pos")
   lim = _np(env, "scene", "robot", "data", "soft_joint_pos_limits")
-  want = np.sum(-np.minimum(q - lim[..., 0], 0) + np.maximum(q - lim[..., 1], 0), 1)
+  want = F64.joint_pos_limits(q, lim[..., 0], lim[..., 1])
   np.testing.assert_allclose(mdp.joint_pos_limits(env, cfg()).numpy(), want, rtol=1e-5, atol=1e-6)
 
 
@@ -137,19 +138,19 @@ def test_feet_terms(env):
   """rewards.py:123-288: air time, clearance, slip, soft landing (command-gated)."""
   c = env.command_manager.get_command("t").numpy().astype(np.float64)
   t = _np(env, "scene", "feet", "data", "current_air_time")
-  want = np.sum((t > 0.05) & (t < 0.5), 1) * _active(c, 0.5)
+  want = F64.feet_air_time(t, 0.05, 0.5, c, 0.5)
   np.testing.assert_allclose(mdp.feet_air_time(env, "feet", 0.05, 0.5, "t", 0.5).numpy(), want)
   z = _np(env, "scene", "robot", "data", "site_pos_w")[..., 2]
-  vxy = np.linalg.norm(_np(env, "scene", "robot", "data", "site_lin_vel_w")[..., :2], axis=-1)
+  vxy = _np(env, "scene", "robot", "data", "site_lin_vel_w")[..., :2]
   np.testing.assert_allclose(mdp.feet_clearance(env, 0.1, "t", 0.01, cfg(site_ids=[0, 1])).numpy(),
-                             np.sum(np.abs(z - 0.1) * vxy, 1) * _active(c, 0.01), rtol=1e-5)
-  inc = (_np(env, "scene", "feet", "data", "found") > 0).astype(np.float64)
+                             F64.feet_clearance(z, vxy, 0.1, c, 0.01), rtol=1e-5)
+  found = _np(env, "scene", "feet", "data", "found")
   np.testing.assert_allclose(mdp.feet_slip(env, "feet", "t", 0.01, cfg(site_ids=[0, 1])).numpy(),
-                             np.sum(vxy ** 2 * inc, 1) * _active(c, 0.01), rtol=1e-5)
-  fm = np.linalg.norm(_np(env, "scene", "feet", "data", "force"), axis=-1)
+                             F64.feet_slip(vxy, found, c, 0.01), rtol=1e-5)
   first = env.scene["feet"].first.numpy()
   np.testing.assert_allclose(mdp.soft_landing(env, "feet", "t", 0.05).numpy(),
-                             np.sum(fm * first, 1) * _active(c, 0.05), rtol=1e-5)
+                             F64.soft_landing(_np(env, "scene", "feet", "data", "force"), first, _active(c, 0.05)),
+                             rtol=1e-5)
 
 
 def test_feet_swing_height_stateful(env):
@@ -159,11 +160,10 @@ def test_feet_swing_height_stateful(env):
   z = _np(env, "scene", "robot", "data", "site_pos_w")[..., 2]
   found = _np(env, "scene", "feet", "data", "found")
   first = env.scene["feet"].first.numpy()
-  peak = np.where(found == 0, np.maximum(0.0, z), 0.0)
-  want = np.sum(((peak / 0.1) - 1.0) ** 2 * first, 1) * _active(c, 0.01)
+  want, peak_after, _ = F64.swing_height(np.zeros_like(z), z, found, first, 0.1, _active(c, 0.01))
   out = term(env, "feet", 0.1, "t", 0.01, cfg(site_ids=[0, 1])).numpy()
   np.testing.assert_allclose(out, want, rtol=1e-5, atol=1e-6)
-  np.testing.assert_allclose(term.peak_heights.numpy(), np.where(first, 0.0, peak), rtol=1e-6)
+  np.testing.assert_allclose(term.peak_heights.numpy(), peak_after, rtol=1e-6)
 
 
 def test_observations(env):

@@ -11,8 +11,10 @@ Python is unpinned (importing it was denied)."""
 import math
 from types import SimpleNamespace as NS
 
+import numpy as np
 import torch
 
+import fp64_terms as F64
 from mjlab_amd import tracking as tr
 from mjlab_amd.math_utils import (matrix_from_quat, quat_error_magnitude, quat_from_euler_xyz,
                                   quat_mul, subtract_frame_transforms, yaw_quat)
@@ -117,9 +119,14 @@ def test_reward_and_termination_formulas():
   r = tr.motion_global_anchor_position_error_exp(env, "m", std=0.3)
   exp = torch.exp(-((c.b_pos[:, 1] - c.r_pos[:, 1]) ** 2).sum(-1) / 0.09)
   torch.testing.assert_close(r, exp)
+  # and the shared fp64 restatement the fused-kernel tests use (fp32 exponents of up to ~60)
+  exp = F64.exp_kernel(((c.b_pos[:, 1] - c.r_pos[:, 1]).numpy().astype(np.float64) ** 2).sum(-1), 0.3)
+  np.testing.assert_allclose(r.numpy(), exp, rtol=1e-4, atol=1e-30)
   r = tr.motion_global_anchor_orientation_error_exp(env, "m", std=0.4)
   exp = torch.exp(-quat_error_magnitude(c.b_quat[:, 1], c.r_quat[:, 1]) ** 2 / 0.16)
   torch.testing.assert_close(r, exp)
+  exp = F64.exp_kernel(F64.quat_error_magnitude(c.b_quat[:, 1].numpy(), c.r_quat[:, 1].numpy()) ** 2, 0.4)
+  np.testing.assert_allclose(r.numpy(), exp, rtol=1e-4, atol=1e-6)
   c.body_pos_relative_w = c.b_pos + 0.1
   r = tr.motion_relative_body_position_error_exp(env, "m", std=0.3, body_names=("b0", "b2"))
   err = ((c.body_pos_relative_w - c.r_pos)[:, [0, 2]] ** 2).sum(-1).mean(-1)
@@ -149,24 +156,67 @@ def test_anchor_observations():
   assert tr.robot_body_ori_b(env, "m").shape == (4, 18)
 
 
-def test_adaptive_sampling_probabilities():
-  """`commands.py:272-290`: uniform floor + replicate-padded causal kernel, normalised."""
+def _sampling_cmd(n=6, nbin=11, T=500):
   c = _Cmd()
-  c.bin_count = 11
+  c.bin_count = nbin
   c.cfg = NS(adaptive_uniform_ratio=0.1, adaptive_kernel_size=3, adaptive_lambda=0.8,
-             body_names=c.cfg.body_names)
+             adaptive_alpha=0.25, sampling_mode="adaptive", body_names=c.cfg.body_names)
   k = torch.tensor([0.8 ** i for i in range(3)])
   c.kernel = k / k.sum()
-  c.bin_failed_count = torch.zeros(11)
+  c.bin_failed_count = torch.zeros(nbin)
+  c._current_bin_failed = torch.zeros(nbin)
+  c.motion = NS(time_step_total=T)
+  c.time_steps = torch.zeros(n, dtype=torch.long)
+  c.metrics = {k: torch.zeros(n) for k in ("sampling_entropy", "sampling_top1_prob", "sampling_top1_bin")}
+  c._env = NS(num_envs=n, device="cpu", termination_manager=NS(terminated=torch.zeros(n, dtype=torch.bool)))
+  return c
+
+
+def test_adaptive_sampling_probabilities():
+  """`commands.py:272-290`: uniform floor + replicate-padded causal kernel, normalised
+  (the fp64 restatement is the one the fused-kernel tests compare k_bins with)."""
+  c = _sampling_cmd()
   c.bin_failed_count[4] = 1.0
   p = c._sampling_probabilities()
   assert abs(float(p.sum()) - 1.0) < 1e-6
-  base = c.bin_failed_count + 0.1 / 11
-  padded = torch.cat([base, base[-1:].repeat(2)])
-  exp = torch.stack([(padded[i:i + 3] * c.kernel).sum() for i in range(11)])
-  torch.testing.assert_close(p, exp / exp.sum())
+  exp = F64.sampling_probabilities(c.bin_failed_count.numpy(), 0.1, c.kernel.numpy())
+  np.testing.assert_allclose(p.numpy(), exp, rtol=1e-5)
   assert int(p.argmax()) in (2, 3, 4)  # the failed bin pulls mass onto itself and its predecessors
   assert math.isclose(float(p[5:].min()), float(p[5:].max()), rel_tol=1e-5)
+
+
+def test_sampling_metrics_change_only_on_a_resample():
+  """`commands.py:258-300, 377-411`: failure counts, probabilities and the three sampling
+  metrics are computed inside _resample_command; an update with no env at the motion end
+  applies the EMA and leaves the metrics alone.  The index path only calls
+  _resample_command with envs to resample; the sync-free masked path runs on every update and
+  selects the new values with mask.any()."""
+  c = _sampling_cmd()
+  c.bin_failed_count[3] = 2.0
+  c.time_steps[:] = torch.tensor([10, 200, 499, 500, 260, 40])
+  c._env.termination_manager.terminated[:] = torch.tensor([True, False, True, True, False, False])
+  mask = torch.tensor([True, True, True, True, False, False])
+  c._adaptive_sampling_masked(mask)
+  want_cbf = np.bincount(F64.current_bins([10, 499, 500], 11, 500), minlength=11)
+  np.testing.assert_array_equal(c._current_bin_failed.numpy(), want_cbf)
+  p = F64.sampling_probabilities(c.bin_failed_count.numpy(), 0.1, c.kernel.numpy())
+  m = F64.sampling_metrics(p)
+  for i, k in enumerate(("sampling_entropy", "sampling_top1_prob", "sampling_top1_bin")):
+    np.testing.assert_allclose(c.metrics[k].numpy(), np.full(6, m[i]), rtol=1e-5)
+  c._adaptive_update()
+  np.testing.assert_allclose(c.bin_failed_count.numpy(),
+                             0.75 * np.eye(11)[3] * 2.0 + 0.25 * want_cbf, rtol=1e-6)
+  assert float(c._current_bin_failed.abs().max()) == 0.0
+  # no env resamples: counts and metrics keep their values although the probabilities moved
+  c._adaptive_sampling_masked(torch.zeros(6, dtype=torch.bool))
+  for i, k in enumerate(("sampling_entropy", "sampling_top1_prob", "sampling_top1_bin")):
+    np.testing.assert_allclose(c.metrics[k].numpy(), np.full(6, m[i]), rtol=1e-5)
+  assert float(c._current_bin_failed.abs().max()) == 0.0
+  # and the next resample sees the moved counts
+  c._adaptive_sampling_masked(torch.tensor([False, True, False, False, False, False]))
+  m2 = F64.sampling_metrics(F64.sampling_probabilities(c.bin_failed_count.numpy(), 0.1, c.kernel.numpy()))
+  assert abs(m2[0] - m[0]) > 1e-3
+  np.testing.assert_allclose(c.metrics["sampling_entropy"].numpy(), np.full(6, m2[0]), rtol=1e-5)
 
 
 def test_task_registered():
