@@ -2718,8 +2718,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     }
     sync();
     STAMP(3);
-    // deterministic order: bitonic sort of (key, slot) over 64 lanes, then permute (more than
-    // 64 contacts: a rank sort, the permutation applied field by field)
+    // deterministic order, ascending key: a rank sort, lane per contact through registers (more
+    // than 64 contacts: the permutation kept in LDS and applied field by field)
     int ncon = min(ints[0], d.nconmax);
     {
       // contact parameters (mj_contactParam semantics) of sorted contact c
@@ -2776,38 +2776,34 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         return b1 | b2 << 8 | m.body_rootid[b1] << 16 | m.body_rootid[b2] << 24;
       };
       if (kCon1<SP> || ncon <= kWave) {
-        int key = lane < ncon ? Si[L.con_key + lane] : 0x7fffffff;
-        int idx = lane;
-#pragma unroll
-        for (int k = 2; k <= kWave; k <<= 1) {
-#pragma unroll
-          for (int j = k >> 1; j > 0; j >>= 1) {
-            int pk = __shfl_xor(key, j);
-            int pi = __shfl_xor(idx, j);
-            bool up = (lane & k) == 0;
-            bool lower = (lane & j) == 0;
-            bool sw = lower ? (up ? key > pk : key < pk) : (up ? key < pk : key > pk);
-            if (sw) { key = pk; idx = pi; }
-          }
+        // rank sort in registers: lane c holds slot c and counts the keys below its own (the
+        // keys pair * 8 + k are distinct), one v_readlane broadcast per contact and no
+        // dependent cross-lane chain; it then writes its contact at that position.  No or one
+        // contact: already in order.
+        const int nc = __builtin_amdgcn_readfirstlane(ncon);
+        int pos = lane;
+        if (nc > 1) {
+          const int key = lane < nc ? Si[L.con_key + lane] : 0x7fffffff;
+          pos = 0;
+          for (int j = 0; j < nc; j++) pos += __builtin_amdgcn_readlane(key, j) < key ? 1 : 0;
         }
-        // lane holds the source slot of sorted position `lane`
         int g1 = 0, g2 = 0;
         float dist = 0, px = 0, py = 0, pz = 0, nx = 0, ny = 0, nz = 0;
         if (lane < ncon) {
-          g1 = Si[L.con_g1 + idx]; g2 = Si[L.con_g2 + idx]; dist = S[L.con_dist + idx];
-          px = S[L.con_pos + 3 * idx]; py = S[L.con_pos + 3 * idx + 1]; pz = S[L.con_pos + 3 * idx + 2];
-          nx = S[L.con_n + 3 * idx]; ny = S[L.con_n + 3 * idx + 1]; nz = S[L.con_n + 3 * idx + 2];
+          g1 = Si[L.con_g1 + lane]; g2 = Si[L.con_g2 + lane]; dist = S[L.con_dist + lane];
+          px = S[L.con_pos + 3 * lane]; py = S[L.con_pos + 3 * lane + 1]; pz = S[L.con_pos + 3 * lane + 2];
+          nx = S[L.con_n + 3 * lane]; ny = S[L.con_n + 3 * lane + 1]; nz = S[L.con_n + 3 * lane + 2];
         }
         sync();
         if (lane < ncon) {
-          Si[L.con_g1 + lane] = g1; Si[L.con_g2 + lane] = g2; S[L.con_dist + lane] = dist;
-          Si[L.con_key + lane] = con_bodies(g1, g2);
-          S[L.con_pos + 3 * lane] = px; S[L.con_pos + 3 * lane + 1] = py; S[L.con_pos + 3 * lane + 2] = pz;
+          Si[L.con_g1 + pos] = g1; Si[L.con_g2 + pos] = g2; S[L.con_dist + pos] = dist;
+          Si[L.con_key + pos] = con_bodies(g1, g2);
+          S[L.con_pos + 3 * pos] = px; S[L.con_pos + 3 * pos + 1] = py; S[L.con_pos + 3 * pos + 2] = pz;
           // contact frame (mju_makeFrame): the unit normal; tangents by cframe() at use
           V3 n = {nx, ny, nz};
           n = n * (1.0f / fmaxf(norm(n), MINVAL));
-          st3(S + L.con_n + 3 * lane, n);
-          contact_params(lane, g1, g2, dist);
+          st3(S + L.con_n + 3 * pos, n);
+          contact_params(pos, g1, g2, dist);
         }
       } else if constexpr (!kCon1<SP>) {
         // rank sort (keys pair * 8 + k are distinct): sorted position of slot c = the number
@@ -2993,6 +2989,71 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       // of 20 active lanes of 64)
       const int ngrp = nvp <= kWave / 2 ? kWave / nvp : 1;
       const int grp = lane / nvp;
+      // element i of contact c's rows, from the contact's values (both loops below)
+      auto con_jrows = [&](int i, uint64_t bm, V3 cang, V3 clin, int cb, V3 pos, V3 com1, V3 com2,
+                           const CFrame& F, int dim, int r0, float mu0, float mu1) {
+        const int b1 = cb_b1(cb), b2 = cb_b2(cb);
+        V3 jd = {0, 0, 0};
+        if (b2 > 0 && ((bm >> b2) & 1ull)) jd = jd + clin + cross(cang, pos - com2);
+        if (b1 > 0 && ((bm >> b1) & 1ull)) jd = jd - (clin + cross(cang, pos - com1));
+        float jn = dot(F.n, jd);
+        if (dim == 1) {
+          Jg[r0 * nvp + i] = jn;
+        } else {
+          float jt1 = dot(F.t, jd);
+          float jt2 = dot(F.b, jd);
+          Jg[(r0 + 0) * nvp + i] = jn + mu0 * jt1;
+          Jg[(r0 + 1) * nvp + i] = jn - mu0 * jt1;
+          Jg[(r0 + 2) * nvp + i] = jn + mu1 * jt2;
+          Jg[(r0 + 3) * nvp + i] = jn - mu1 * jt2;
+        }
+      };
+      if (con1 && ngrp == 1 && nvp <= kWave) {
+        // One lane per dof and the contacts taken in turn by every lane: lane c forms contact
+        // c's values once (frame, position, friction, first row, bodies, root coms) and keeps
+        // them in registers; the loop's contact index is wave-uniform, so every iteration takes
+        // them by v_readlane and reads no LDS (iteration c + 1 waits for nothing of c's).
+        const int i = lane;
+        int kcb = 0, kdim = 0, kr0 = 0;
+        float kmu0 = 0, kmu1 = 0;
+        V3 kpos = {0, 0, 0}, kc1 = {0, 0, 0}, kc2 = {0, 0, 0};
+        CFrame kF = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        if (lane < ncon) {
+          kcb = Si[L.con_key + lane];
+          kdim = cdim;
+          kr0 = lim_total + con_off;
+          kmu0 = S[L.con_mu + 2 * lane]; kmu1 = S[L.con_mu + 2 * lane + 1];
+          kpos = v3(S + L.con_pos + 3 * lane);
+          kF = cframe(v3(S + L.con_n + 3 * lane));
+          kc1 = v3(S + L.subtree_com + 3 * cb_r1(kcb));
+          kc2 = v3(S + L.subtree_com + 3 * cb_r2(kcb));
+        }
+        uint64_t bm = 0;
+        V3 cang = {0, 0, 0}, clin = {0, 0, 0};
+        if (i < nvp) {
+          for (int r = 0; r < lim_total && r < nefc; r++) {
+            const int jd = Si[L.efc_cid + r] >> 2;
+            Jg[r * nvp + i] = (jd >> 8) == i ? S[L.efc_D + r] : 0.f;
+          }
+          if (i >= nv) {  // zero padding columns of the contact rows
+            for (int r = lim_total; r < nefc; r++) Jg[r * nvp + i] = 0.f;
+          } else {
+            bm = m.dof_bodymask[i];
+            const float* cd = S + L.cdof + 6 * i;
+            cang = v3(cd); clin = v3(cd + 3);
+          }
+        }
+        const auto rli = [](int v, int l) { return __builtin_amdgcn_readlane(v, l); };
+        const auto rl3 = [](V3 v, int l) { return V3{rl(v.x, l), rl(v.y, l), rl(v.z, l)}; };
+        const int nc = __builtin_amdgcn_readfirstlane(ncon);
+        for (int c = 0; c < nc; c++) {
+          const int cb = rli(kcb, c), dim = rli(kdim, c), r0 = rli(kr0, c);
+          const float mu0 = rl(kmu0, c), mu1 = rl(kmu1, c);
+          const V3 pos = rl3(kpos, c), com1 = rl3(kc1, c), com2 = rl3(kc2, c);
+          const CFrame F = {rl3(kF.n, c), rl3(kF.t, c), rl3(kF.b, c)};
+          if (i < nv) con_jrows(i, bm, cang, clin, cb, pos, com1, com2, F, dim, r0, mu0, mu1);
+        }
+      } else
       for (int i = lane - grp * nvp; grp < ngrp && i < nvp; i += kWave) {
         // limits
         for (int r = grp; r < lim_total && r < nefc; r += ngrp) {
@@ -3008,27 +3069,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         V3 cang = v3(cd), clin = v3(cd + 3);
         for (int c = grp; c < ncon; c += ngrp) {
           const int cb = Si[L.con_key + c];
-          const int b1 = cb_b1(cb), b2 = cb_b2(cb);
-          V3 pos = v3(S + L.con_pos + 3 * c);
-          V3 jd = {0, 0, 0};
-          if (b2 > 0 && ((bm >> b2) & 1ull))
-            jd = jd + clin + cross(cang, pos - v3(S + L.subtree_com + 3 * cb_r2(cb)));
-          if (b1 > 0 && ((bm >> b1) & 1ull))
-            jd = jd - (clin + cross(cang, pos - v3(S + L.subtree_com + 3 * cb_r1(cb))));
-          const CFrame F = cframe(v3(S + L.con_n + 3 * c));
-          float jn = dot(F.n, jd);
-          int r0 = Si[L.con_efc + c];
-          if (Si[L.con_dim + c] == 1) {
-            Jg[r0 * nvp + i] = jn;
-          } else {
-            float jt1 = dot(F.t, jd);
-            float jt2 = dot(F.b, jd);
-            float mu0 = S[L.con_mu + 2 * c], mu1 = S[L.con_mu + 2 * c + 1];
-            Jg[(r0 + 0) * nvp + i] = jn + mu0 * jt1;
-            Jg[(r0 + 1) * nvp + i] = jn - mu0 * jt1;
-            Jg[(r0 + 2) * nvp + i] = jn + mu1 * jt2;
-            Jg[(r0 + 3) * nvp + i] = jn - mu1 * jt2;
-          }
+          con_jrows(i, bm, cang, clin, cb, v3(S + L.con_pos + 3 * c),
+                    v3(S + L.subtree_com + 3 * cb_r1(cb)), v3(S + L.subtree_com + 3 * cb_r2(cb)),
+                    cframe(v3(S + L.con_n + 3 * c)), Si[L.con_dim + c], Si[L.con_efc + c],
+                    S[L.con_mu + 2 * c], S[L.con_mu + 2 * c + 1]);
         }
       }
       sync();
