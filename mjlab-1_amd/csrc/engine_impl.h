@@ -186,38 +186,62 @@ __device__ __forceinline__ void sync() { __syncthreads(); }
 #define MF(f) (m.f + (size_t)w * m.f##_ws)
 
 // Diagnostic build only (-DMJX_STAMPS): per-stage s_memtime deltas, accumulated in
-// registers and added to D.prof once per wave at kernel end (STAMP_FLUSH) -- per-stamp global
+// registers and added to D.prof once per wave at kernel end (flush) -- per-stamp global
 // atomics sit in vmcnt and would charge their contention to the next memory wait.
+// step_body opens one Stamps per world and phase and hands it to every stage by reference;
+// without MJX_STAMPS it is empty and every call is nothing.
 #ifdef MJX_STAMPS
-#define STAMP(k)                                                                 \
-  do {                                                                           \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                          \
-    unsigned long long t_ = __builtin_amdgcn_s_memtime();                         \
-    stamp_acc[k] += t_ - stamp_prev;                                             \
-    stamp_prev = t_;                                                             \
-  } while (0)
-// SUBSTAMP(k): nested split of the Newton stage into slots 16+ (does not advance STAMP).
-#define SUBSTAMP(k)                                                              \
-  do {                                                                           \
-    __builtin_amdgcn_s_waitcnt(0xC07F);                                          \
-    unsigned long long t_ = __builtin_amdgcn_s_memtime();                         \
-    stamp_acc[16 + (k)] += t_ - sub_prev;                                        \
-    sub_prev = t_;                                                               \
-  } while (0)
-// Only worlds with at least P->stamp_minrows constraint rows this substep are counted
-// (MJX355_STAMP_MINROWS: the breakdown of the heavy worlds); slot 47 counts flushes.
-#define STAMP_FLUSH()                                                            \
-  do {                                                                           \
-    if (lane == 0 && D.nefc[w] >= P->stamp_minrows) {                            \
-      stamp_acc[47] = 1;                                                         \
-      for (int k_ = 0; k_ < 48; k_++)                                            \
-        if (stamp_acc[k_]) atomicAdd((unsigned long long*)&D.prof[k_], stamp_acc[k_]); \
-    }                                                                            \
-  } while (0)
+struct Stamps {
+  unsigned long long wt0, prev, sub_prev, acc[48];
+  __device__ __forceinline__ void open() {
+    wt0 = __builtin_amdgcn_s_memrealtime();
+    prev = __builtin_amdgcn_s_memtime();
+    sub_prev = prev;
+#pragma unroll
+    for (int k = 0; k < 48; k++) acc[k] = 0;
+  }
+  // stage slot k: the time since the previous stamp
+  __device__ __forceinline__ void stamp(int k) {
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    acc[k] += t - prev;
+    prev = t;
+  }
+  // nested split of a stage (the preamble, the Newton solver, the integration) into slots
+  // 16+ (does not advance stamp)
+  __device__ __forceinline__ void sub(int k) {
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    acc[16 + k] += t - sub_prev;
+    sub_prev = t;
+  }
+  __device__ __forceinline__ void sub_restart() { sub_prev = __builtin_amdgcn_s_memtime(); }
+  // event counters (slots 38-46)
+  __device__ __forceinline__ void count(int k, int n) { acc[k] += n; }
+  // Only worlds with at least P->stamp_minrows constraint rows this substep are counted
+  // (MJX355_STAMP_MINROWS: the breakdown of the heavy worlds); slot 47 counts flushes.
+  __device__ __forceinline__ void flush(const Params* P, int ph, int w, int lane) {
+    const DData& D = P->D;
+    if (lane == 0 && D.nefc[w] >= P->stamp_minrows) {
+      acc[47] = 1;
+      for (int k = 0; k < 48; k++)
+        if (acc[k]) atomicAdd((unsigned long long*)&D.prof[k], acc[k]);
+    }
+    if (lane == 0) {
+      D.wtrace[(size_t)w * 8 + 2 * ph] = wt0;
+      D.wtrace[(size_t)w * 8 + 2 * ph + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+  }
+};
 #else
-#define STAMP(k) do {} while (0)
-#define SUBSTAMP(k) do {} while (0)
-#define STAMP_FLUSH() do {} while (0)
+struct Stamps {
+  __device__ __forceinline__ void open() {}
+  __device__ __forceinline__ void stamp(int) {}
+  __device__ __forceinline__ void sub(int) {}
+  __device__ __forceinline__ void sub_restart() {}
+  __device__ __forceinline__ void count(int, int) {}
+  __device__ __forceinline__ void flush(const Params*, int, int, int) {}
+};
 #endif
 
 // --------------------------------------------------------------------------- tiled SPD algebra
@@ -1816,13 +1840,23 @@ constexpr bool lean_spec() {
 template <int SP> constexpr bool kLean = lean_spec<SP>();
 #define MJX_PHASE_ATTR __attribute__((amdgpu_waves_per_eu(PH == 1 && kLean<SP> ? 4 : (PH == 1 || PH == 0) && NR <= 48 ? 3 : 1)))
 #define MJX_PHASE_ATTR_B __attribute__((amdgpu_waves_per_eu(NR <= 48 ? 3 : 1)))
+// One world through phase PH (0 = A, 1 = B, 2 = C) in the wave's LDS S: the
+// common body of every step kernel.
 // LAT selects the latency form of phase B (step_newton_lat below): the same algorithm with
 // more registers in flight, for the launch that holds the heavy worlds.
 // LAT: bit 0 the latency form of phase B (else the throughput form), bit 1 (phase B only) the
 // constraint Jacobian read from the B pack in global memory (carve kLdsJG)
+// `integrate`: the integrator switch, read by phases A and C only (0: a forward pass).
+// `row_class`: which Newton launch this is, read by the world selection and phase B only.
+//    -1  every world of the range in the full-capacity carve (no work list: the re-solve and
+//        the masked forward),
+//     0  the full-capacity class: the worlds past every class capacity, or all worlds of a
+//        model without row classes,
+//   k>0  class k (launch_step, classify_kernel): the worlds with row_cap[k-2] < nefc <=
+//        row_cap[k-1], in the class carve P->LP[2 + k]; the pack keeps the full-capacity layout.
 template <int NR, int PH, int SP, int LAT>
 __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* __restrict__ P, int w0,
-                                          int w1, int sel, int last, int integrate,
+                                          int w1, int sel, int last, int integrate, int row_class,
                                           const uint8_t* __restrict__ mask, const int bid) {
   const auto& d = dims_of<SP>(P);
   const Opt& o = P->o;
@@ -1830,14 +1864,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   const DData& D = P->D;
   // phase B: `integrate` carries the Newton row class (0 = full capacity, k > 0 = LP[2 + k])
   constexpr bool JG = PH == 1 && (LAT & 2) != 0;
-  const Lds& L = (PH == 1 && integrate > 0) ? P->LP[2 + integrate]
+  const Lds& L = (PH == 1 && row_class > 0) ? P->LP[2 + row_class]
                                             : lds_of<SP, JG ? kLdsJG : PH>(P);
   const auto& LB = lds_of<SP, 1>(P);
   const auto& LC = lds_of<SP, 2>(P);
   if (sel & kSelPrio) __builtin_amdgcn_s_setprio(3);
   int w = w0 + bid;
-  const int sel_arg = sel;  // (phase C's contact-sensor code has a local `sel`)
-  (void)sel_arg;
   const int split = sel & 0xff;
   const int cls1 = (sel >> 8) & 0xff;
   if (sel & kSelOvf) {
@@ -1849,8 +1881,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     if constexpr (PH == 1) {
       // Newton by row class: workgroup i takes the i-th world of its class's list
       // (classify_kernel: rows descending, masked worlds only)
-      if (P->nrowclass > 0 && integrate >= 0) {  // integrate < 0: every world, full carve
-        const int* seg = P->wl_seg + 2 * ((kRowClasses + 1) * split + integrate);
+      if (P->nrowclass > 0 && row_class >= 0) {  // row_class < 0: every world, full carve
+        const int* seg = P->wl_seg + 2 * ((kRowClasses + 1) * split + row_class);
         if (bid >= seg[1]) return;
         w = P->wl_list[seg[0] + bid];
       }
@@ -1872,7 +1904,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   // (list-driven launches -- a Newton row class, a class pipeline's C -- never see them:
   // classify_kernel left them out, and their one extra dependent load stays off the chain)
   if (PH != 0 && P->ovf_resolve && !(sel & kSelOvf) && !cls1 &&
-      !(PH == 1 && P->nrowclass > 0 && integrate >= 0) && P->ovf_flag[w])
+      !(PH == 1 && P->nrowclass > 0 && row_class >= 0) && P->ovf_flag[w])
     return;
   // ... and a range chain's next phase A (models without row classes: step_chain over every
   // world of a batch range) skips it too: the re-solve chain runs that world's next A
@@ -1889,14 +1921,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   const int nvq = (nvp + 3) & ~3;  // copy length of an nvp vector region
   const float h = o.timestep;
   (void)nq; (void)nu; (void)h;
-#ifdef MJX_STAMPS
-  const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
-  unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
-  unsigned long long sub_prev = stamp_prev;
-  unsigned long long stamp_acc[48];
-#pragma unroll
-  for (int k_ = 0; k_ < 48; k_++) stamp_acc[k_] = 0;
-#endif
+  Stamps st;
+  st.open();
   const float* body_pos = MF(body_pos);
   const float* body_quat = MF(body_quat);
   const float* body_ipos = MF(body_ipos);
@@ -1927,7 +1953,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     // lane-aligned inputs stay in registers (lane u: ctrl[u], lane i: qfrc_applied[i])
     const float ctrl_u = lane < nu ? D.ctrl[(size_t)w * nu + lane] : 0.f;
     const float qapp_i = lane < nv ? D.qfrc_applied[(size_t)w * nv + lane] : 0.f;
-    SUBSTAMP(15);
+    st.sub(15);
     float* Jg = gw + LB.efc_J;
     const BodyPtrs BP{body_pos, body_quat, body_ipos, body_iquat, body_mass, body_inertia,
                       jnt_pos, jnt_axis, qpos0};
@@ -1935,7 +1961,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
 #ifdef MJX_STAMPS
     __builtin_amdgcn_s_waitcnt(0);
 #endif
-    SUBSTAMP(16);
+    st.sub(16);
     const bool bl = lane < nb;  // this lane holds a body record
     DofRec Dr;
     {
@@ -1955,7 +1981,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
 #ifdef MJX_STAMPS
     __builtin_amdgcn_s_waitcnt(0);
 #endif
-    SUBSTAMP(17);
+    st.sub(17);
     const ActRec Ar = load_act(m, MF(actuator_gear), MF(actuator_gainprm), MF(actuator_biasprm),
                                MF(actuator_forcerange), MF(actuator_ctrlrange),
                                min(lane, max(nu - 1, 0)));
@@ -1964,7 +1990,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     any_xfrc = __any(any_xfrc);
     lds_dma_wait();
     sync();
-    SUBSTAMP(13);
+    st.sub(13);
     // =========================================================== kinematics
     // (1) lane per body: the body frame in its parent's frame (body offset, then its
     //     joints) and the joint anchors / axes in that frame; free-joint, mocap and world
@@ -2054,7 +2080,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     }
     if (bl) st4(S + L.xquat + 4 * B.b, qnorm(kq));
     sync();
-    SUBSTAMP(14);
+    st.sub(14);
     // body rotations stay quaternions in LDS (xmat / ximat are formed where used)
     const Q4 xq = bl ? q4(S + L.xquat + 4 * B.b) : Q4{1.f, 0.f, 0.f, 0.f};
     if (bl) st3(S + L.xipos + 3 * B.b, v3(S + L.xpos + 3 * B.b) + qrot(xq, B.ipos));
@@ -2066,7 +2092,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         st3(S + L.xaxis + 3 * k, qrot(qp, v3(S + L.xaxis + 3 * k)));
       }
     }
-    STAMP(0);
+    st.stamp(0);
     // =========================================================== com / cinert / cdof
     // Subtree sums as broadcast loops: lane b adds body c's term when c is in its subtree
     // (B.sub); every lane reads the same LDS address per c, no level-by-level syncs.
@@ -2183,7 +2209,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         qmat(S + L.sxmat + 9 * s, qmul(qb, q4(squat + 4 * s)));
       }
     }
-    STAMP(1);
+    st.stamp(1);
     // =========================================================== CRB + mass matrix
     {
       // composite rigid-body inertia = cinert summed over the subtree (broadcast loop)
@@ -2231,7 +2257,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     // then contacts).  Phase C gets the implicit-integration factor of M + h D instead
     // (below, scratch region F, also LTR).
     store_ltr(gw + LB.M, S + L.M, nvp, lane);
-    STAMP(2);
+    st.stamp(2);
     // =========================================================== velocity stage
     // cvel(b) = sum over the dofs moving b of cdof * qvel: broadcast loop over the dofs
     {
@@ -2413,7 +2439,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       st3(S + L.stang + 3 * b, mulv(Ri, hl));
     }
     sync();
-    STAMP(6);
+    st.stamp(6);
     if (integrate) {
       // implicitfast / Euler: factor M + h diag(dof damping - gear^2 biasprm2) here, where M
       // and the (clamped) actuator forces are at hand, into the scratch region F; phase C then
@@ -2458,7 +2484,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     // space) is reused by the geom frames at collision
     const float qacs_i = lane < nvq ? S[L.qacc_smooth + lane] : 0.f;
     if (lane < nvq) gw[LB.qacc_smooth + lane] = qacs_i;
-    STAMP(7);
+    st.stamp(7);
     // subtree com velocity and angular momentum about the subtree com, as sums over the
     // subtree (broadcast loop): V = sum m vc / M, L = sum h + sum m (x - X) x (vc - V) --
     // the closed form of the child-to-parent recursion (parallel-axis shifts)
@@ -2505,7 +2531,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
     }
     sync();
-    STAMP(8);
+    st.stamp(8);
     if (lane == 0) { ints[0] = 0; ints[1] = 0; ints[2] = 0; ints[3] = 0; }
     // geom frames (here, not in kinematics: their LDS aliases regions dead after RNE)
     {
@@ -2717,7 +2743,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
     }
     sync();
-    STAMP(3);
+    st.stamp(3);
     // deterministic order, ascending key: a rank sort, lane per contact through registers (more
     // than 64 contacts: the permutation kept in LDS and applied field by field)
     int ncon = min(ints[0], d.nconmax);
@@ -2850,7 +2876,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
       sync();
     }
-    STAMP(4);
+    st.stamp(4);
     // =========================================================== constraints
     {
       // row counts: limits (lane per joint) then contacts (lane per contact)
@@ -2900,7 +2926,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const bool over = ints[0] > d.nconmax || nefc > d.njmax;
         int slot = -1;
         if (over && lane == 0) {
-          const int li = 2 * split + ((sel_arg & kSelAPar) ? 1 : 0);
+          const int li = 2 * split + ((sel & kSelAPar) ? 1 : 0);
           slot = atomicAdd(P->ovf_n + li, 1);
           if (slot < P->ovf_cap) {
             P->ovf_list[(size_t)li * P->ovf_cap + slot] = w;
@@ -3132,7 +3158,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     const int nefc = ints[1];
     ncon = ints[4];
     if (lane == 0) D.nefc[w] = nefc;  // every substep: classify_kernel sorts the Newton work by it
-    STAMP(5);
+    st.stamp(5);
     // =========================================================== sensors
     // (pos / vel stage: the last substep's only, see the subtree momenta above)
     for (int s = lane; obs && s < d.nsensor; s += kWave) {
@@ -3242,7 +3268,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         }
       }
     }
-    STAMP(11);
+    st.stamp(11);
     // outputs final after phase A
 #ifdef MJX_ABLATE_OUTPUTS
     if (false) {
@@ -3311,7 +3337,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
       if (lane == 0) { D.ncon[w] = ncon; D.nefc[w] = nefc; wsv[6] = nout; wsv[7] = ncon; }
     }
-    STAMP(12);
+    st.stamp(12);
     // hand-off: B pack (J rows already written) and the A part of the C pack; the contact
     // arrays only up to the live contacts (phase C reads none past ncon)
     const int C = ncon;
@@ -3340,14 +3366,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       cp4(gc + LC.con_dim, S + L.con_dim, C4, lane);
       cp4(gc + LC.con_efc, S + L.con_efc, C4, lane);
     }
-    STAMP(14);
+    st.stamp(14);
   } else if constexpr (PH == 1) {
     // ----------------------------------------------------------- phase B (Newton)
     {
       const int nefc_in = reinterpret_cast<const int*>(gw)[LB.ints + 1];
       // row classes (launch_step, classify_kernel): class k > 0 holds the worlds with
       // row_cap[k-2] < nefc <= row_cap[k-1], class 0 the rest (all worlds without classes)
-      const int cls = integrate;
+      const int cls = row_class;
       // B pack: carve offsets == pack offsets; M's slot holds M in LTR form (the rest of the
       // slot is neither written nor read)
       cp_pack(S, gw, L.M + ltr_size(nvp), lane);
@@ -3382,7 +3408,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     float Mt[2][16];  // M as register tiles; its LDS slot becomes H / jt_mul scratch
     tiles_load_ltr(Mt, T, S + L.M);
     sync();
-    STAMP(15);
+    st.stamp(15);
     // =========================================================== Newton solver
     int niter = 0;
     if (nefc == 0) {
@@ -3402,11 +3428,9 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       int* act = Si + L.efc_act;
       float* Lm = S + L.H;
       const float scale = 1.0f / (o.meaninertia * (float)max(nv, 1));
-#ifdef MJX_STAMPS
-      sub_prev = __builtin_amdgcn_s_memtime();
-      stamp_acc[38] += 1;         // solves with rows
-      stamp_acc[39] += !tree_h;   // of them with the dense factor (a contact across branches)
-#endif
+      st.sub_restart();
+      st.count(38, 1);         // solves with rows
+      st.count(39, !tree_h);   // of them with the dense factor (a contact across branches)
       // With at most one row per lane (every world of the bulk row class) the solver keeps
       // its row's D, J x - aref (rja) and, in the line search, J s (rjs) in registers: the
       // per-row loops below then read no LDS.  Lanes past nefc hold zeros (v = 0 is never
@@ -3482,7 +3506,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         rqs = S[L.qacc_smooth + lane];
         rfs = S[L.qfrc_smooth + lane];
       }
-      SUBSTAMP(0);
+      st.sub(0);
       unsigned long long act_sig[4] = {~0ull, ~0ull, ~0ull, ~0ull};
       for (int iter = 0; iter < o.iterations; iter++) {
         // gradient = M x - qfrc_smooth + J_act^T (D jar)
@@ -3492,12 +3516,15 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
                                   : build_active(act, jar, nefc, lane, act_sig, &same_set, &nchg);
         // H depends on the active set only: unchanged set -> reuse the stored factor (exact)
         const bool refactor = iter == 0 || !same_set;
+        // (under the ifdef although count() is empty without it: arguments that read nchg
+        // keep build_active's change count alive into the optimiser and shift the whole
+        // kernel's code, ~0.2 % on G1)
 #ifdef MJX_STAMPS
-        stamp_acc[40] += 1;
-        stamp_acc[41] += refactor && iter > 0;
-        stamp_acc[42] += iter > 0 ? nchg : 0;
-        stamp_acc[43] += refactor && iter > 0 && nchg <= 4;
-        stamp_acc[44] += iter == 0 ? nact : 0;
+        st.count(40, 1);
+        st.count(41, refactor && iter > 0);
+        st.count(42, iter > 0 ? nchg : 0);
+        st.count(43, refactor && iter > 0 && nchg <= 4);
+        st.count(44, iter == 0 ? nact : 0);
 #endif
         (void)nchg;
         if (reg_rows) {
@@ -3519,7 +3546,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         }
         gn = sqrtf(wave_sum(gn));
         gr = sqrtf(wave_sum(gr));
-        SUBSTAMP(1);
+        st.sub(1);
         // MuJoCo's gradient test; floor = fp32 rounding scale of the summed terms
         if (iter > 0 && scale * gn < fmaxf(o.tolerance, 16.f * FLT_EPSILON * scale * gr)) break;
         // Hessian H = M + J_act^T D J_act in register tiles, factor, solve
@@ -3540,7 +3567,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
 #endif
         }
         sync();
-        SUBSTAMP(2);
+        st.sub(2);
         {
           float R[NR];
           float rd;
@@ -3567,7 +3594,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
 #endif
           }
           sync();
-          SUBSTAMP(3);
+          st.sub(3);
           // the tree-form factor is of the reversed matrix: lane i solves for dof nvp-1-i
           const int pl = tree_h ? nvp - 1 - lane : lane;
           float xs = lane < nvp ? S[L.srch + pl] : 0.f;
@@ -3580,7 +3607,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (lane < nvp) S[L.srch + pl] = xs;
           sync();
         }
-        SUBSTAMP(4);
+        st.sub(4);
         matvec_rows(Js, J, S + L.srch, nefc, nvp, lane);
         tiles_symv(Mt, T, S + L.srch, S + L.Ms, nvp, lane);
         float g1 = 0.f, sn = 0.f, sv = 0.f;
@@ -3598,7 +3625,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const float gtol = o.tolerance * o.ls_tolerance * sn / scale;
         // the line search's J s (constant across its evaluations) in a register too
         const float rjs = reg_rows && lane < nefc ? Js[lane] : 0.f;
-        SUBSTAMP(5);
+        st.sub(5);
         // exact line search on the piecewise-quadratic cost (same algorithm as the oracle)
         // The derivative is a sum of O(nefc) terms; once |der| is within its fp32
         // rounding floor the root of the piecewise-linear derivative has been found to
@@ -3652,9 +3679,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           bool done = false;
           for (int it = 0; it < o.ls_iterations; it++) {
             float der, der2, nz;
-#ifdef MJX_STAMPS
-            stamp_acc[45] += 1;
-#endif
+            st.count(45, 1);
             ls_eval(a, &der, &der2, &nz);
             if (fabsf(der) <= fmaxf(gtol, nz)) { alpha = a; done = true; break; }
             if (der < 0) { lo = a; best = a; } else { hi = a; }
@@ -3664,12 +3689,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             a = next;
           }
           if (!done) alpha = best > 0 ? best : a;
-#ifdef MJX_STAMPS
-          stamp_acc[46] += 1;
-#endif
+          st.count(46, 1);
         }
         niter = iter + 1;
-        SUBSTAMP(6);
+        st.sub(6);
         if (alpha == 0.f) break;
         if (lane < nvp) {
           rx = rx + alpha * S[L.srch + lane];
@@ -3686,7 +3709,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         sync();
         float old = cost;
         cost = cost_now();
-        SUBSTAMP(7);
+        st.sub(7);
         // MuJoCo's improvement test, with the fp32 resolution of the cost (a sum of
         // non-negative terms, so its rounding error is ~eps*|cost|) as the floor: below
         // it, further iterations only chase rounding noise.
@@ -3708,9 +3731,9 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
                                 : build_active(act, jar, nefc, lane, sig_f, &same_f);
       sync();
       jt_mul(S + L.qfrc_con, J, wv, act, nact, nvp, lane);
-      SUBSTAMP(8);
+      st.sub(8);
     }
-    STAMP(9);
+    st.stamp(9);
     if (lane == 0) ints[5] = niter;
     sync();
     cp4(gc + LC.ints, S + L.ints, 8, lane);
@@ -3726,7 +3749,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
       if (lane == 0) D.solver_niter[w] = niter;
     }
-    STAMP(14);
+    st.stamp(14);
   } else {
     // ----------------------------------------------------------- phase C
     // C pack (carve offsets == pack offsets): before the last substep of a fused step only
@@ -3754,7 +3777,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     const int nefc = ints[1];
     int ncon = ints[4];
     const int niter_last = ints[5];
-    STAMP(15);
+    st.stamp(15);
     // =========================================================== post-constraint acc
     // cacc(b) = cacc_v(b) + sum over the dofs moving b of cdof * qacc, cacc_v(b) = -gravity
     // + sum cdofdot * qvel from phase A's RNE (broadcast loop over the dofs, no level syncs);
@@ -3780,7 +3803,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       }
     }
     sync();
-    STAMP(10);
+    st.stamp(10);
     // =========================================================== sensors
     for (int s = lane; s < d.nsensor; s += kWave) {
       float* out = D.sensordata + (size_t)w * d.nsensordata + m.sensor_adr[s];
@@ -3900,7 +3923,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     if (kCon1<SP> || ncon <= kWave)
       contact_sensors_wave(S, Si, L, m, d, D.sensordata + (size_t)w * d.nsensordata, ncon,
                            o.maxmatch, last || P->outputs_every, P, lane);
-    STAMP(11);
+    st.stamp(11);
     if (last) {
       size_t wb = (size_t)w * nb;
       for (int i = lane; i < 6 * nb; i += kWave) D.cacc[wb * 6 + i] = S[L.cacc + i];
@@ -3932,19 +3955,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       ws[lane] = (lane >= 2 && lane <= 4) ? old + v : max(old, v);
       if (lane >= 2 && lane <= 4 && v) atomicAdd(D.evtotal + lane - 2, v);
     }
-    STAMP(12);
-#ifdef MJX_STAMPS
-    sub_prev = __builtin_amdgcn_s_memtime();
-#endif
+    st.stamp(12);
+    st.sub_restart();
     if (integrate) {
       sync();
     // =========================================================== implicitfast / Euler
     sync();
     {
-      SUBSTAMP(9);
+      st.sub(9);
       // (M + h D) qacc' = qfrc_smooth + qfrc_constraint with the factor phase A stored in
       // the world's scratch (rows and columns come straight from global memory)
-      SUBSTAMP(10);
+      st.sub(10);
       {
         float rd;
         rows_scale_factor_ltr<NR>(Fa, rd, Fdv, nvp, lane);
@@ -3955,7 +3976,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         if (lane < nvp && pl < nv) S[L.qvel + pl] += h * acc;
       }
       sync();
-      SUBSTAMP(11);
+      st.sub(11);
       for (int k = lane; k < d.njnt; k += kWave) {
         int a = m.jnt_qposadr[k], dof = m.jnt_dofadr[k];
         int t = m.jnt_type[k];
@@ -3974,7 +3995,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       for (int i = lane; i < nv; i += kWave) S[L.qacc_ws + i] = S[L.x + i];
       time += h;
       sync();
-      SUBSTAMP(12);
+      st.sub(12);
     }
 
       for (int i = lane; i < nq; i += kWave) D.qpos[(size_t)w * nq + i] = S[L.qpos + i];
@@ -4007,15 +4028,9 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       // read of the ring has no side effect); lane u alone touches actuator u's column
       if (P->act_on && P->act.ring_len > 0) act_push(P->act, w, lane, nu);
     }
-    STAMP(13);
+    st.stamp(13);
   }
-  STAMP_FLUSH();
-#ifdef MJX_STAMPS
-  if (lane == 0) {
-    D.wtrace[(size_t)w * 8 + 2 * PH] = wt0;
-    D.wtrace[(size_t)w * 8 + 2 * PH + 1] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
+  st.flush(P, PH, w, lane);
 }
 
 // An overflow re-solve launch (step_ovf) has a fixed grid (kOvfGrid, captured in graphs);
@@ -4034,7 +4049,9 @@ __global__ __launch_bounds__(kWave) MJX_PHASE_ATTR void step_phase(const Params*
                                                     int sel, int last, int integrate,
                                                     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
-  step_body<NR, PH, SP, false>(S, P, w0, w1, sel, last, integrate, mask, (int)blockIdx.x);
+  // the StepFn argument: phase B's Newton row class, phases A and C's integrator switch
+  step_body<NR, PH, SP, false>(S, P, w0, w1, sel, last, PH == 1 ? 0 : integrate,
+                               PH == 1 ? integrate : 0, mask, (int)blockIdx.x);
 }
 // Phase B for the full-capacity row class (the heavy worlds: more constraint rows than the
 // class capacity) and the masked forward.  That launch holds a few hundred worlds on 256 CUs,
@@ -4048,20 +4065,20 @@ __global__ __launch_bounds__(kWave) MJX_PHASE_ATTR void step_phase(const Params*
 // SIMD running a heavy world keeps two bulk-class waves beside it instead of one
 template <int NR, int SP, int JGL = 1, int CAP = 0>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(CAP ? 3 : 1, CAP ? 8 : 2))) void step_newton_lat(
-    const Params* __restrict__ P, int w0, int w1, int sel, int last, int integrate,
+    const Params* __restrict__ P, int w0, int w1, int sel, int last, int row_class,
     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
-  step_body<NR, 1, SP, JGL>(S, P, w0, w1, sel, last, integrate, mask, (int)blockIdx.x);
+  step_body<NR, 1, SP, JGL>(S, P, w0, w1, sel, last, 0, row_class, mask, (int)blockIdx.x);
 }
 // The full-capacity class's Newton in the throughput form (3 waves / SIMD) with J in global
 // memory: for batches whose heavy worlds are many (jump hfield: ~5,400 of 16,384 at 84-137
 // rows), where that launch is throughput-bound, not one world's latency.
 template <int NR, int SP>
 __global__ __launch_bounds__(kWave) MJX_PHASE_ATTR_B void step_phase_jg(
-    const Params* __restrict__ P, int w0, int w1, int sel, int last, int integrate,
+    const Params* __restrict__ P, int w0, int w1, int sel, int last, int row_class,
     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
-  step_body<NR, 1, SP, 2>(S, P, w0, w1, sel, last, integrate, mask, (int)blockIdx.x);
+  step_body<NR, 1, SP, 2>(S, P, w0, w1, sel, last, 0, row_class, mask, (int)blockIdx.x);
 }
 
 // The overflow re-solve launches (sel & kSelOvf; ovf_chain): a fixed grid of kOvfGrid
@@ -4093,7 +4110,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   for (int bid = (int)blockIdx.x;; bid += (int)gridDim.x) {
-    step_body<NR, PH, SP, LAT>(S, P, w0, w1, sel, last, integrate, mask, bid);
+    step_body<NR, PH, SP, LAT>(S, P, w0, w1, sel, last, PH == 1 ? 0 : integrate,
+                               PH == 1 ? integrate : 0, mask, bid);
     if (!ovf_more(P, sel, bid + (int)gridDim.x)) break;
   }
   ovf_clear_on_exit(P, sel);
@@ -4116,13 +4134,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     }
   }
   for (int bid = (int)blockIdx.x;; bid += (int)gridDim.x) {
-    step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, mask, bid);
+    step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
     __threadfence();  // the packs this wave stored are read back by the next phase
     __syncthreads();
-    step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, -1, mask, bid);
+    step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, 0, /*row_class=*/-1, mask, bid);
     __threadfence();
     __syncthreads();
-    step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, mask, bid);
+    step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
     if (!ovf_more(P, sel, bid + (int)gridDim.x)) break;
   }
   ovf_clear_on_exit(P, sel);
@@ -4154,13 +4172,13 @@ __attribute__((amdgpu_waves_per_eu((LAT & 1) ? 1 : (kLean<SP> ? 4 : NR <= 48 ? 3
   const int bid = (int)blockIdx.x;
   const int split = sel & 0xff;
   const int cls1 = (sel >> 8) & 0xff;  // class + 1
-  step_body<NR, 1, SP, LAT>(S, P, w0, w1, split, last, cls1 - 1, mask, bid);
+  step_body<NR, 1, SP, LAT>(S, P, w0, w1, split, last, 0, /*row_class=*/cls1 - 1, mask, bid);
   chain_handoff();
-  step_body<NR, 2, SP, 0>(S, P, w0, w1, split | cls1 << 8, last, integrate, mask, bid);
+  step_body<NR, 2, SP, 0>(S, P, w0, w1, split | cls1 << 8, last, integrate, 0, mask, bid);
   if (sel & kSelChainA) {
     chain_handoff();
     step_body<NR, 0, SP, 0>(S, P, w0, w1, split | cls1 << 8 | (sel & kSelAPar) | kSelFusedA,
-                                (sel & kSelNextLast) ? 1 : 0, integrate, mask, bid);
+                                (sel & kSelNextLast) ? 1 : 0, integrate, 0, mask, bid);
   }
 }
 
@@ -4176,11 +4194,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int bid = (int)blockIdx.x;
   if (w0 + bid >= w1 || !mask[w0 + bid]) return;
-  step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, mask, bid);
+  step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
   chain_handoff();
-  step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, -1, mask, bid);
+  step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, 0, /*row_class=*/-1, mask, bid);
   chain_handoff();
-  step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, mask, bid);
+  step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
 }
 
 using StepFn = void (*)(const Params*, int, int, int, int, int, const uint8_t*);
