@@ -224,6 +224,27 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
   if (desc->abi_version != MJX_ABI_VERSION) return fail("ABI version mismatch");
   if (desc->nbody > mjx::kMaxBodies) return fail("at most 64 bodies per world supported");
   if (desc->nv > mjx::kMaxDof) return fail("at most 64 dofs per world supported");
+  // Phase B holds M and the Newton Hessian as two 4x4 register tiles per lane (engine_impl.h
+  // Tiles): 128 tiles, the lower triangle of 60 padded dofs.  64 padded dofs have 136, and the
+  // step would drop the last eight.
+  if (desc->nv > 60)
+    return fail("at most 60 dofs per world supported (61 to 64 need a third register tile per lane)");
+  // Phase A moves a tree's frames back to the world with a lane shuffle indexed by the root's
+  // body id, while lanes hold bodies in level order (level_body): the lane read must hold the
+  // root itself, or, for a root that is not free, any body that is not free (both add zero).
+  if (desc->nbody > 0 && desc->level_body && desc->body_rootid) {
+    auto is_free = [&](int b) {
+      return desc->body_jntnum[b] > 0 && desc->jnt_type[desc->body_jntadr[b]] == 0;
+    };
+    for (int b = 1; b < desc->nbody; b++) {
+      const int r = desc->body_rootid[b];
+      if (r < 0 || r >= desc->nbody) return fail("body_rootid out of range");
+      const int x = desc->level_body[r];
+      if (x != r && (is_free(r) || is_free(x)))
+        return fail("a tree that follows a tree of several bodies is not supported: its root's "
+                    "body id is not its level-order lane (one articulated tree, then single bodies)");
+    }
+  }
   if (desc->nu > mjx::kMaxLanes || desc->njnt > mjx::kMaxLanes)
     return fail("at most 64 actuators and 64 joints per world supported");
   if (desc->cone != 0) return fail("only pyramidal cones are supported");
