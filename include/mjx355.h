@@ -219,6 +219,53 @@ typedef struct mjxActuatorDesc {
 size_t mjx_actuator_desc_size(void);
 int mjx_sim_set_actuators(mjxSim* sim, const mjxActuatorDesc* desc, void* stream);
 
+/* Learned actuators (mjlab_amd/actuator.py: LearnedMlpActuator), bound after
+ * mjx_sim_set_actuators.  Actuator u with net[u] != 255 must be of kind 3 there (a DC motor,
+ * its kp and kd unused): its PD term t is replaced by the output of MLP net[u] on the last
+ * `history` frames (e, v) = (pt - q, qd) of its joint -- the current substep's (pt read late as
+ * for any delayed actuator) and history - 1 before it:
+ *   input = [e_0 .. e_{H-1} | v_0 .. v_{H-1}], e scaled by pos_scale, v by vel_scale, index =
+ *   lag; input_order 1 puts the velocities first.  A lag is clamped to the frames pushed since
+ *   the reset; with none pushed every lag reads the current frame.
+ *   x <- activation_l(W_l x + b_l) for l < nlayer (fp32, fused multiply-adds);
+ *   t = x[0] * torque_scale, then the kind-3 clip above.
+ * width[l] / width[l + 1] are layer l's input / output widths: width[0] = 2 * history, every
+ * width <= 32, width[nlayer] = 1; activation[l]: 0 none, 1 relu, 2 softsign, 3 tanh, 4 elu
+ * (alpha 1), none after the last layer.  weight[l] is host [width[l + 1], width[l]] row-major,
+ * bias[l] host [width[l + 1]]: copied into device memory the sim owns (freed on the next
+ * binding, a null descriptor, mjx_sim_set_actuators and mjx_sim_destroy).
+ * history [nworld, hist_len, 2, nu] (hist_len = the largest history - 1; frames oldest first,
+ * e then v), staging [nworld, 2, nu] and pushes [nworld, nu] are device buffers of the
+ * caller's: phase A stores the frame it used in staging, and every integrated substep (not a
+ * forward) shifts an actuator's last history - 1 frames by one, appends the staged frame and
+ * counts the push, saturating at history - 1.  A reset of a world is the caller's: zero its
+ * pushes.  With hist_len = 0 the three may be null.  Synchronises. */
+#define MJX_MAX_ACT_NETS 4
+#define MJX_MAX_NET_LAYERS 4
+typedef struct mjxActuatorNet {
+  int32_t nlayer;            /* 1..4 linear layers */
+  int32_t history;           /* 1..8 frames */
+  int32_t input_order;       /* 0: [pos | vel], 1: [vel | pos] */
+  int32_t reserved;
+  int32_t width[MJX_MAX_NET_LAYERS + 1];
+  int32_t activation[MJX_MAX_NET_LAYERS];
+  float pos_scale, vel_scale, torque_scale;
+  const float* weight[MJX_MAX_NET_LAYERS];
+  const float* bias[MJX_MAX_NET_LAYERS];
+} mjxActuatorNet;
+typedef struct mjxActuatorNetDesc {
+  int32_t nworld, nu;
+  int32_t nnet;              /* 1..4 */
+  int32_t hist_len;          /* max over the networks of history - 1 */
+  mjxActuatorNet nets[MJX_MAX_ACT_NETS];
+  const uint8_t* net;        /* host [nu]: network of actuator u, 255: none */
+  float* history;
+  float* staging;
+  int32_t* pushes;
+} mjxActuatorNetDesc;
+size_t mjx_actuator_net_desc_size(void);
+int mjx_sim_set_actuator_nets(mjxSim* sim, const mjxActuatorNetDesc* desc, void* stream);
+
 /* Diagnostics: per-sim counters as int32[8] written to host `out` ([0] max contacts, [1] max
  * rows seen, [2] contact-overflow, [3] row-overflow, [4] unsupported-pair events -- dropped
  * work --, [5] max Newton iterations, [6] worlds re-solved at the max capacity); synchronises

@@ -91,8 +91,13 @@ struct mjxSim_ {
   float* air_buf[5] = {};
   bool act_on = false;  // explicit actuators (mjx_sim_set_actuators)
   mjx::ActParams act{};
+  mjx::NetParams net{};   // learned actuators (mjx_sim_set_actuator_nets)
+  float* netw = nullptr;  // packed actuator-network weights (mjx_sim_set_actuator_nets)
   int spec = 0;  // model specialisation in use (mjx::find_spec), 0 = generic kernels
   mjx::SideStream side{};  // streams of the Newton row classes (when classes are used)
+  mjxSim_() {
+    for (int u = 0; u < mjx::kWave; u++) net.net_of[u] = mjx::kNoNet;  // as drop_actuator_nets leaves it
+  }
   ~mjxSim_() {
     for (int p = 0; p < mjx::kMaxSplit; p++) {
       if (side.fork[p]) (void)hipEventDestroy(side.fork[p]);
@@ -159,6 +164,7 @@ static mjx::Params host_params(const mjxSim_* s) {
   p.air_lc = s->air_buf[3]; p.air_time = s->air_buf[4];
   p.act_on = s->act_on ? 1 : 0;
   p.act = s->act;
+  p.net = s->net;
   static const int minrows = [] {
     const char* e = getenv("MJX355_STAMP_MINROWS");
     return e ? atoi(e) : 0;
@@ -819,6 +825,7 @@ int mjx_sim_destroy(mjxSim* s) {
   if (s->gscr_big) (void)hipFree(s->gscr_big);
   if (s->ovf) (void)hipFree(s->ovf);
   if (s->dparams_big) (void)hipFree(s->dparams_big);
+  if (s->netw) (void)hipFree(s->netw);
   for (void* p : s->expanded_allocs) (void)hipFree(p);
   delete s;
   return 0;
@@ -866,9 +873,24 @@ int mjx_sim_track_air_time(mjxSim* s, int n, const int32_t* found_adr, float* cu
 
 size_t mjx_actuator_desc_size(void) { return sizeof(mjxActuatorDesc); }
 
+// Unbind the actuator networks (host side; the caller uploads the parameters).  The stream is
+// drained first: a launch in flight may still read the weights.
+static int drop_actuator_nets(mjxSim_* s, void* stream) {
+  if (s->netw) {
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipDeviceSynchronize());
+    (void)hipFree(s->netw);
+    s->netw = nullptr;
+  }
+  s->net = mjx::NetParams{};
+  for (int u = 0; u < mjx::kWave; u++) s->net.net_of[u] = mjx::kNoNet;
+  return 0;
+}
+
 int mjx_sim_set_actuators(mjxSim* s, const mjxActuatorDesc* a, void* stream) {
   if (!a) {  // off: phase A takes every actuator's ctrl as it is
     if (!s) return fail("null sim");
+    if (drop_actuator_nets(s, stream)) return -1;
     s->act_on = false;
     s->act = mjx::ActParams{};
     return sync_params(s, stream);
@@ -920,8 +942,108 @@ int mjx_sim_set_actuators(mjxSim* s, const mjxActuatorDesc* a, void* stream) {
   p.pt = a->position_target; p.vt = a->velocity_target; p.ft = a->effort_target;
   p.ring = a->ring; p.lag = a->lag; p.pushes = a->pushes; p.draws = a->draws;
   p.hold = a->hold;
+  if (drop_actuator_nets(s, stream)) return -1;  // a new binding has no networks yet
   s->act = p;
   s->act_on = true;
+  return sync_params(s, stream);
+}
+
+size_t mjx_actuator_net_desc_size(void) { return sizeof(mjxActuatorNetDesc); }
+
+int mjx_sim_set_actuator_nets(mjxSim* s, const mjxActuatorNetDesc* a, void* stream) {
+  const std::string who = "mjx_sim_set_actuator_nets: ";
+  if (!a) {  // off: the bound actuators keep their kinds, the learned ones fall back to kp = kd = 0
+    if (!s) return fail(who + "null sim");
+    if (drop_actuator_nets(s, stream)) return -1;
+    return sync_params(s, stream);
+  }
+  static_assert(MJX_MAX_ACT_NETS == mjx::kMaxNets && MJX_MAX_NET_LAYERS == mjx::kMaxNetLayers, "");
+  // the descriptor's own consistency first (it needs no sim), then its fit to the sim
+  if (a->nworld < 1) return fail(who + "nworld < 1");
+  if (a->nu < 1 || a->nu > mjx::kWave) return fail(who + "1 <= nu <= 64");
+  if (a->nnet < 1 || a->nnet > mjx::kMaxNets) return fail(who + "1 <= nnet <= 4");
+  int hmax = 0;
+  for (int k = 0; k < a->nnet; k++) {
+    const mjxActuatorNet& n = a->nets[k];
+    if (n.nlayer < 1 || n.nlayer > mjx::kMaxNetLayers) return fail(who + "1 <= nlayer <= 4");
+    if (n.history < 1 || n.history > mjx::kMaxNetHist) return fail(who + "1 <= history <= 8");
+    if (n.input_order != 0 && n.input_order != 1)
+      return fail(who + "input_order must be 0 (pos_vel) or 1 (vel_pos)");
+    for (int l = 0; l <= n.nlayer; l++)
+      if (n.width[l] < 1 || n.width[l] > mjx::kMaxNetWidth) return fail(who + "1 <= width <= 32");
+    if (n.width[0] != 2 * n.history) return fail(who + "the input width must be 2 * history");
+    if (n.width[n.nlayer] != 1) return fail(who + "the output width must be 1");
+    for (int l = 0; l < n.nlayer; l++) {
+      if (n.activation[l] < mjx::kNetNone || n.activation[l] > mjx::kNetElu)
+        return fail(who + "activation must be 0 (none), 1 (relu), 2 (softsign), 3 (tanh) or 4 (elu)");
+      if (!n.weight[l] || !n.bias[l]) return fail(who + "null weight / bias");
+    }
+    if (n.activation[n.nlayer - 1] != mjx::kNetNone)
+      return fail(who + "no activation after the last layer");
+    hmax = n.history - 1 > hmax ? n.history - 1 : hmax;
+  }
+  if (a->hist_len != hmax) return fail(who + "hist_len must be the largest history - 1");
+  if (!a->net) return fail(who + "null net table");
+  bool any = false;
+  for (int u = 0; u < a->nu; u++) {
+    if (a->net[u] != mjx::kNoNet && a->net[u] >= a->nnet) return fail(who + "net[u] out of range");
+    any |= a->net[u] != mjx::kNoNet;
+  }
+  if (!any) return fail(who + "no actuator has a network (pass a null descriptor to unbind)");
+  if (hmax > 0 && (!a->history || !a->staging || !a->pushes))
+    return fail(who + "null history / staging / pushes buffer");
+  if (!s) return fail(who + "null sim");
+  if (a->nworld != s->nworld) return fail(who + "nworld differs from the sim's");
+  if (a->nu != s->d.nu) return fail(who + "nu differs from the model's");
+  if (!s->act_on) return fail(who + "no explicit actuators bound (mjx_sim_set_actuators comes first)");
+  for (int u = 0; u < a->nu; u++)
+    if (a->net[u] != mjx::kNoNet && s->act.kind[u] != mjx::kActDcMotor)
+      return fail(who + "net[u] on an actuator whose kind is not 3 (DC motor)");
+  // pack: per layer [32][32] W (row = output, zero padded) then 32 biases
+  std::vector<float> w((size_t)a->nnet * mjx::kNetStride, 0.f);
+  for (int k = 0; k < a->nnet; k++) {
+    const mjxActuatorNet& n = a->nets[k];
+    for (int l = 0; l < n.nlayer; l++) {
+      float* dst = w.data() + (size_t)k * mjx::kNetStride + (size_t)l * mjx::kNetLayerStride;
+      const int nin = n.width[l], nout = n.width[l + 1];
+      for (int o = 0; o < nout; o++) {
+        for (int i = 0; i < nin; i++) dst[o * mjx::kMaxNetWidth + i] = n.weight[l][(size_t)o * nin + i];
+        dst[mjx::kMaxNetWidth * mjx::kMaxNetWidth + o] = n.bias[l][o];
+      }
+    }
+  }
+  if (drop_actuator_nets(s, stream)) return -1;
+  // (from here the old networks are gone: a failure uploads the cleared parameters, so the
+  // device never keeps the freed pointer)
+  hipError_t e = hipMalloc((void**)&s->netw, w.size() * sizeof(float));
+  if (e == hipSuccess)
+    e = hipMemcpy(s->netw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (s->netw) (void)hipFree(s->netw);
+    s->netw = nullptr;
+    (void)sync_params(s, stream);
+    return fail(who + "weight upload: " + hipGetErrorString(e));
+  }
+  mjx::NetParams& p = s->net;
+  p.nnet = a->nnet;
+  p.hist_len = hmax;
+  p.netw = s->netw;
+  p.hist = a->history; p.stage = a->staging; p.hpush = a->pushes;
+  for (int k = 0; k < a->nnet; k++) {
+    const mjxActuatorNet& n = a->nets[k];
+    mjx::NetMeta& M = p.net[k];
+    M = mjx::NetMeta{};
+    M.nlayer = (uint8_t)n.nlayer; M.hist = (uint8_t)n.history; M.vel_first = (uint8_t)n.input_order;
+    for (int l = 0; l < n.nlayer; l++) {
+      M.nin[l] = (uint8_t)n.width[l]; M.nout[l] = (uint8_t)n.width[l + 1];
+      M.act[l] = (uint8_t)n.activation[l];
+    }
+    M.pos_scale = n.pos_scale; M.vel_scale = n.vel_scale; M.torque_scale = n.torque_scale;
+  }
+  for (int u = 0; u < mjx::kWave; u++) {
+    p.net_of[u] = u < a->nu ? a->net[u] : (uint8_t)mjx::kNoNet;
+    p.net_hist[u] = p.net_of[u] != mjx::kNoNet ? (uint8_t)a->nets[p.net_of[u]].history : 0;
+  }
   return sync_params(s, stream);
 }
 

@@ -159,6 +159,20 @@ int register_spec(const Dims& d, const int* par, int npar, StepFnPtr (*fn)(int))
 // and the torch-owned per-world buffers, each [nworld, nu] but the ring.
 constexpr int kActBuiltin = 0, kActDelayed = 1, kActIdealPd = 2, kActDcMotor = 3;
 constexpr int kMaxActLag = 32;  // frames per world of the delay ring
+// Actuator networks: plain MLPs of at most kMaxNetLayers linear layers, every width at most
+// kMaxNetWidth, 2 * hist inputs, one output.  A network's weights are packed per layer as
+// [kMaxNetWidth][kMaxNetWidth] row-major W (row = output, zero padded) followed by
+// kMaxNetWidth biases, so every offset is a compile-time constant.
+constexpr int kMaxNets = 4, kMaxNetLayers = 4, kMaxNetWidth = 32, kMaxNetHist = 8;
+constexpr int kNetLayerStride = kMaxNetWidth * kMaxNetWidth + kMaxNetWidth;
+constexpr int kNetStride = kMaxNetLayers * kNetLayerStride;
+constexpr int kNoNet = 255;
+constexpr int kNetNone = 0, kNetRelu = 1, kNetSoftsign = 2, kNetTanh = 3, kNetElu = 4;
+struct NetMeta {
+  uint8_t nlayer, hist, vel_first, pad;  // vel_first: the input is [vel | pos] ("vel_pos")
+  uint8_t nin[kMaxNetLayers], nout[kMaxNetLayers], act[kMaxNetLayers];
+  float pos_scale, vel_scale, torque_scale;
+};
 struct ActParams {
   uint8_t kind[kWave];     // actuator u is lane u (nu <= kWave)
   uint8_t min_lag[kWave], max_lag[kWave];
@@ -170,6 +184,22 @@ struct ActParams {
   float* ring;             // [nworld, ring_len, nu] past position targets, oldest first
   int *lag, *pushes, *draws;
   const int* hold;           // nonzero: the lag is pinned, the push draws no new one (may be null)
+};
+// Learned actuators (mjx_sim_set_actuator_nets): actuator u with net_of[u] != kNoNet is a
+// kind-3 actuator whose PD term is the output of MLP net_of[u] on the last net[].hist
+// frames (pt - q, qd) of its joint (net_torque in engine_impl.h).  Read only by the kPhNet
+// kernel variants, and kept at the end of Params: the other kernels' code does not change
+// with it.
+struct NetParams {
+  int nnet;                // networks bound (0: none)
+  int hist_len;            // frames per world in `hist`: the largest net's hist - 1
+  NetMeta net[kMaxNets];
+  uint8_t net_of[kWave];   // network of actuator u, kNoNet: none
+  uint8_t net_hist[kWave]; // net[net_of[u]].hist, 0 where there is none
+  const float* netw;       // [nnet][kNetStride] packed weights, device memory the sim owns
+  float* hist;             // [nworld, hist_len, 2, nu] past frames, oldest first
+  float* stage;            // [nworld, 2, nu] the frame phase A used, pushed by phase C
+  int* hpush;              // [nworld, nu] frames pushed since the reset, at most hist - 1
 };
 
 // Everything a launch needs, resident in device memory (read through the scalar cache
@@ -225,6 +255,7 @@ struct Params {
   int* ovf_flag;   // [nworld]
   int* ovf_done;   // [kMaxSplit][2] workgroups through the list's last launch (it clears the list)
   int con_stride;  // contact slots per world of the contact output arrays (the max capacity)
+  NetParams net;   // learned actuators (with act_on; the kPhNet kernels)
 };
 
 // `sel` launch argument of the step kernels: bits 0-7 batch split, 8-15 row class + 1 (the
@@ -317,8 +348,18 @@ enum PhaseCode : int {
   kPhNewtonJG = 10,     // throughput Newton, J in global memory (step_phase_jg)
   kPhChainLatJG = 11,   // the full-capacity class's latency chain, J in global memory
   kPhNewtonLatCap = 12, // latency Newton at the throughput kernels' register budget (heavy_cap)
-  kPhaseCodes = 13
+  kPhaseCodes = 13,
+  // or-ed to the code of a kernel that holds a phase A or C (phase_has_net): the variant whose
+  // actuation block evaluates the bound actuator networks and whose integration block pushes
+  // their history (mjx_sim_set_actuator_nets).  step_fn adds it while networks are bound, so
+  // every other launch keeps the kernels it had; the launch counters count a variant under
+  // its plain code.
+  kPhNet = 32
 };
+constexpr bool phase_has_net(int ph) {
+  return ph == kPhA || ph == kPhC || ph == kPhOvfNextA || ph == kPhResolve || ph == kPhChain ||
+         ph == kPhChainLat || ph == kPhMasked || ph == kPhChainLatJG;
+}
 // LDS carve index of a launch's Newton part: Params::LP[carve], or Params::LPJ for kLdsJG
 // (engine_impl.h lds_of).
 enum Carve : int {

@@ -182,9 +182,14 @@ static StepFn spec_fn(int spec, int ph) {
     default: return nullptr;
   }
 }
+static StepFn step_fn(const Params& host, PhaseCode ph, bool net) {
+  const int code = net && phase_has_net(ph) ? ph | kPhNet : ph;
+  StepFn f = host.spec > 0 ? spec_fn(host.spec, code) : nullptr;
+  return f ? f : generic_fn(host.d.nv, code);
+}
+// ... with actuator networks bound, the variant whose phase A evaluates them
 static StepFn step_fn(const Params& host, PhaseCode ph) {
-  StepFn f = host.spec > 0 ? spec_fn(host.spec, ph) : nullptr;
-  return f ? f : generic_fn(host.d.nv, ph);
+  return step_fn(host, ph, host.act_on && host.net.nnet > 0);
 }
 // Launch counters (host side only; mjx_launch_counts): how many launches of each PhaseCode,
 // and of classify_kernel (kLaunchClassify), this process has issued.  Counted
@@ -276,11 +281,14 @@ int find_spec(const Dims& d, const int* dof_parentid) {
 hipError_t prepare_step(const Params& host) {
   for (int ph = 0; ph < kPhaseCodes; ph++) {
     const size_t need = lds_need_max(host, knobs(), PhaseCode(ph));
-    const StepFn f = step_fn(host, PhaseCode(ph));
-    if (need > 64 * 1024 && f) {
-      hipError_t e = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)need);
-      if (e != hipSuccess) return e;
+    // (networks are bound after the sim is made: their variants get the attribute here too)
+    for (int net = 0; net < (phase_has_net(ph) ? 2 : 1); net++) {
+      const StepFn f = step_fn(host, PhaseCode(ph), net != 0);
+      if (need > 64 * 1024 && f) {
+        hipError_t e = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)need);
+        if (e != hipSuccess) return e;
+      }
     }
   }
   return hipSuccess;

@@ -1621,12 +1621,171 @@ __device__ __forceinline__ ActRec load_act(const DModel& m, const float* gear, c
 __device__ __forceinline__ float act_div(float x, float y) {
   return (float)((double)x / (double)y);
 }
+// ---- learned actuators (mjx_sim_set_actuator_nets; LearnedMlpActuator is the torch form)
+// The weights are never written by a kernel: read through the constant address space, a
+// wave-uniform address becomes a scalar load.
+typedef const __attribute__((address_space(4))) float* NetW;
+template <int H>
+__device__ __forceinline__ void net_inputs(float (&x)[kMaxNetWidth], const float (&a)[kMaxNetHist],
+                                           const float (&b)[kMaxNetHist]) {
+#pragma unroll
+  for (int k = 0; k < H; k++) {
+    x[k] = a[k];
+    x[H + k] = b[k];
+  }
+}
+// A wave-uniform word as the compiler can know it: Params reaches phase A through vector
+// loads, so what must sit in SGPRs (the weights' address, a network's metadata) goes through
+// v_readfirstlane; every active lane holds the same value.
+__device__ __forceinline__ uint32_t net_uniform(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+static_assert(sizeof(NetMeta) == 28, "net_torque reads NetMeta as 7 words");
+// The network's torque (before the DC-motor clip) of learned actuator u of world w, 0 for a
+// lane without a network.  The lanes of one network run together, the other lanes inactive:
+// the network index, its metadata and every weight address are wave-uniform, the activations
+// stay in registers under compile-time indices.  The input is the frame (pt - q, qd) and the
+// H - 1 frames before it from `hist`, a lag clamped to the frames pushed since the reset (the
+// delay ring's rule), each scaled once.  The one side effect is the store of the current
+// frame to `stage`, the same value however often a substep's phase A runs; phase C's
+// net_push moves it into `hist`.
+__device__ __forceinline__ float net_torque(const NetParams& A, int w, int u, int nu, float pt,
+                                            float q, float qd) {
+#pragma clang fp contract(off)
+  const int mine = A.net_of[u];
+  if (mine == kNoNet) return 0.f;
+  const size_t i = (size_t)w * nu + u;
+  const float pe = pt - q;
+  const int Hm = A.hist_len;
+  int held = 0;
+  if (Hm > 0) {
+    A.stage[(size_t)w * 2 * nu + u] = pe;
+    A.stage[((size_t)w * 2 + 1) * nu + u] = qd;
+    held = A.hpush[i];
+  }
+  float out = 0.f;
+  const int nnet = (int)net_uniform((uint32_t)A.nnet);
+  const unsigned long long wp = (unsigned long long)A.netw;
+  const float* wbase = reinterpret_cast<const float*>(
+      (unsigned long long)net_uniform((uint32_t)(wp >> 32)) << 32 | net_uniform((uint32_t)wp));
+  for (int k = 0; k < nnet; k++) {
+    if (mine != k) continue;
+    // the lanes of network k: its metadata as scalars (NetMeta's 7 words).  (Under mine == k
+    // the optimiser substitutes the per-lane `mine` for k: ks keeps the index a scalar.)
+    const int ks = (int)net_uniform((uint32_t)k);
+    const uint32_t* mw = reinterpret_cast<const uint32_t*>(&A.net[ks]);
+    const uint32_t m0 = net_uniform(mw[0]), m_in = net_uniform(mw[1]), m_out = net_uniform(mw[2]),
+                   m_act = net_uniform(mw[3]);
+    const int nlayer = m0 & 255, H = (m0 >> 8) & 255, vel_first = (m0 >> 16) & 255;
+    const float ps = __uint_as_float(net_uniform(mw[4])), vs = __uint_as_float(net_uniform(mw[5]));
+    const float ts = __uint_as_float(net_uniform(mw[6]));
+    float a[kMaxNetHist], b[kMaxNetHist];
+    a[0] = pe * ps;
+    b[0] = qd * vs;
+#pragma unroll
+    for (int j = 1; j < kMaxNetHist; j++) {
+      a[j] = b[j] = 0.f;
+      if (j < H) {
+        const int kk = min(j, held);
+        float pj = pe, vj = qd;
+        if (kk > 0) {
+          const float* f = A.hist + (((size_t)w * Hm + (Hm - kk)) * 2) * nu + u;
+          pj = f[0];
+          vj = f[nu];
+        }
+        a[j] = pj * ps;
+        b[j] = vj * vs;
+      }
+    }
+    if (vel_first) {
+#pragma unroll
+      for (int j = 0; j < kMaxNetHist; j++) {
+        const float s = a[j];
+        a[j] = b[j];
+        b[j] = s;
+      }
+    }
+    float x[kMaxNetWidth];
+#pragma unroll
+    for (int j = 0; j < kMaxNetWidth; j++) x[j] = 0.f;
+    switch (H) {
+      case 1: net_inputs<1>(x, a, b); break;
+      case 2: net_inputs<2>(x, a, b); break;
+      case 3: net_inputs<3>(x, a, b); break;
+      case 4: net_inputs<4>(x, a, b); break;
+      case 5: net_inputs<5>(x, a, b); break;
+      case 6: net_inputs<6>(x, a, b); break;
+      case 7: net_inputs<7>(x, a, b); break;
+      default: net_inputs<8>(x, a, b); break;
+    }
+    NetW Wn = (NetW)(wbase + (size_t)ks * kNetStride);
+#pragma unroll 1
+    for (int l = 0; l < nlayer; l++) {
+      NetW W = Wn + l * kNetLayerStride;
+      const int nin = (m_in >> (8 * l)) & 255, nout = (m_out >> (8 * l)) & 255,
+                code = (m_act >> (8 * l)) & 255;
+      float y[kMaxNetWidth];
+#pragma unroll
+      for (int o = 0; o < kMaxNetWidth; o++) {
+        float acc = 0.f;
+        if (o < nout) {
+          acc = W[kMaxNetWidth * kMaxNetWidth + o];
+#pragma unroll
+          for (int c = 0; c < kMaxNetWidth; c += 8) {
+            if (c < nin) {  // (the padding of W and x is zero: a partial chunk adds nothing)
+#pragma unroll
+              for (int t = 0; t < 8; t++) acc = fmaf(W[o * kMaxNetWidth + c + t], x[c + t], acc);
+            }
+          }
+        }
+        y[o] = acc;
+      }
+      // every activation maps the padding's 0 to 0
+      if (code == kNetRelu) {
+#pragma unroll
+        for (int o = 0; o < kMaxNetWidth; o++) x[o] = fmaxf(y[o], 0.f);
+      } else if (code == kNetSoftsign) {
+#pragma unroll
+        for (int o = 0; o < kMaxNetWidth; o++) x[o] = act_div(y[o], 1.0f + fabsf(y[o]));
+      } else if (code == kNetTanh) {
+#pragma unroll
+        for (int o = 0; o < kMaxNetWidth; o++) x[o] = tanhf(y[o]);
+      } else if (code == kNetElu) {
+#pragma unroll
+        for (int o = 0; o < kMaxNetWidth; o++) x[o] = y[o] > 0.f ? y[o] : expm1f(y[o]);
+      } else {
+#pragma unroll
+        for (int o = 0; o < kMaxNetWidth; o++) x[o] = y[o];
+      }
+    }
+    out = x[0] * ts;
+  }
+  return out;
+}
+// After an integrated substep: shift learned actuator u's H - 1 history frames by one, oldest
+// first, and append the frame its phase A staged.
+__device__ __forceinline__ void net_push(const NetParams& A, int w, int u, int nu) {
+  if (u >= nu) return;
+  const int H = A.net_hist[u];
+  if (H < 2) return;
+  const int Hm = A.hist_len;
+  float* h = A.hist + (size_t)w * Hm * 2 * nu + u;
+  for (int k = Hm - (H - 1); k + 1 < Hm; k++) {
+    h[(size_t)(2 * k) * nu] = h[(size_t)(2 * k + 2) * nu];
+    h[(size_t)(2 * k + 1) * nu] = h[(size_t)(2 * k + 3) * nu];
+  }
+  h[(size_t)(2 * Hm - 2) * nu] = A.stage[(size_t)w * 2 * nu + u];
+  h[(size_t)(2 * Hm - 1) * nu] = A.stage[((size_t)w * 2 + 1) * nu + u];
+  const size_t i = (size_t)w * nu + u;
+  A.hpush[i] = min(A.hpush[i] + 1, H - 1);
+}
 // The torque of explicit actuator u of world w (lane u) from the joint's position q and
 // velocity qd: the operations of IdealPdActuator.compute / DcMotorActuator._clip_effort in
 // their order, each rounded once (no contraction), so that the engine and the torch path
 // agree bit for bit.  Reads only: a world's phase A may run more than once per substep.
-__device__ __forceinline__ float explicit_ctrl(const ActParams& A, int w, int u, int nu, float q,
-                                               float qd) {
+template <bool NET>
+__device__ __forceinline__ float explicit_ctrl(const ActParams& A, const NetParams& N, int w, int u,
+                                               int nu, float q, float qd) {
 #pragma clang fp contract(off)
   const size_t i = (size_t)w * nu + u;
   float pt = A.pt[i];
@@ -1639,9 +1798,17 @@ __device__ __forceinline__ float explicit_ctrl(const ActParams& A, int w, int u,
   if (A.kind[u] == kActDelayed) return pt;  // a delayed builtin actuator: its ctrl, late
   // plain operators, which the pragma above keeps apart (the __fmul_rn / __fadd_rn inlines
   // are compiled under their header's contraction mode and were seen fused into v_fmac)
-  float t = A.kp[i] * (pt - q);
-  t = t + A.kd[i] * (A.vt[i] - qd);
-  t = t + A.ft[i];
+  float t = 0.f;
+  bool learned = false;
+  if constexpr (NET) {  // the kernels launched while networks are bound (engine.h kPhNet)
+    learned = N.net_of[u] != kNoNet;
+    t = net_torque(N, w, u, nu, pt, q, qd);
+  }
+  if (!learned) {
+    t = A.kp[i] * (pt - q);
+    t = t + A.kd[i] * (A.vt[i] - qd);
+    t = t + A.ft[i];
+  }
   const float flim = A.flim[i];
   float lo = -flim, hi = flim;
   if (A.kind[u] == kActDcMotor) {
@@ -1838,14 +2005,18 @@ constexpr bool lean_spec() {
   }
 }
 template <int SP> constexpr bool kLean = lean_spec<SP>();
-#define MJX_PHASE_ATTR __attribute__((amdgpu_waves_per_eu(PH == 1 && kLean<SP> ? 4 : (PH == 1 || PH == 0) && NR <= 48 ? 3 : 1)))
+// (a phase A that evaluates actuator networks holds two more 32-register activation arrays:
+// 2 waves / SIMD, so that they stay out of scratch)
+#define MJX_PHASE_ATTR __attribute__((amdgpu_waves_per_eu(NET && PH == 0 ? (NR <= 48 ? 2 : 1) : PH == 1 && kLean<SP> ? 4 : (PH == 1 || PH == 0) && NR <= 48 ? 3 : 1)))
 #define MJX_PHASE_ATTR_B __attribute__((amdgpu_waves_per_eu(NR <= 48 ? 3 : 1)))
 // One world through phase PH (0 = A, 1 = B, 2 = C) in the wave's LDS S: the
 // common body of every step kernel.
 // LAT selects the latency form of phase B (step_newton_lat below): the same algorithm with
 // more registers in flight, for the launch that holds the heavy worlds.
 // LAT: bit 0 the latency form of phase B (else the throughput form), bit 1 (phase B only) the
-// constraint Jacobian read from the B pack in global memory (carve kLdsJG)
+// constraint Jacobian read from the B pack in global memory (carve kLdsJG), bit 2 (phases A
+// and C) the actuation block evaluates the bound actuator networks (net_torque) and the
+// integration block pushes their history (net_push)
 // `integrate`: the integrator switch, read by phases A and C only (0: a forward pass).
 // `row_class`: which Newton launch this is, read by the world selection and phase B only.
 //    -1  every world of the range in the full-capacity carve (no work list: the re-solve and
@@ -1864,6 +2035,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   const DData& D = P->D;
   // phase B: `integrate` carries the Newton row class (0 = full capacity, k > 0 = LP[2 + k])
   constexpr bool JG = PH == 1 && (LAT & 2) != 0;
+  constexpr bool NET = PH == 0 && (LAT & 4) != 0;
+  constexpr bool NETC = PH == 2 && (LAT & 4) != 0;
   const Lds& L = (PH == 1 && row_class > 0) ? P->LP[2 + row_class]
                                             : lds_of<SP, JG ? kLdsJG : PH>(P);
   const auto& LB = lds_of<SP, 1>(P);
@@ -2376,7 +2549,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       float c = ctrl_u;
       if (P->act_on) {  // wave-uniform: explicit actuators are bound (mjx_sim_set_actuators)
         if (P->act.kind[u] != kActBuiltin) {
-          c = explicit_ctrl(P->act, w, u, nu, S[L.qpos + Ar.qa], S[L.qvel + Ar.dof]);
+          c = explicit_ctrl<NET>(P->act, P->net, w, u, nu, S[L.qpos + Ar.qa], S[L.qvel + Ar.dof]);
           if (last) D.ctrl[(size_t)w * nu + u] = c;  // data.ctrl shows the applied torque
         }
       }
@@ -4027,6 +4200,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       // (phase A may run twice -- the overflow re-solve -- and in a masked forward, so its
       // read of the ring has no side effect); lane u alone touches actuator u's column
       if (P->act_on && P->act.ring_len > 0) act_push(P->act, w, lane, nu);
+      // learned actuators: the frame phase A staged joins the network's history
+      if constexpr (NETC) {
+        if (P->act_on && P->net.hist_len > 0) net_push(P->net, w, lane, nu);
+      }
     }
     st.stamp(13);
   }
@@ -4044,14 +4221,14 @@ __device__ __forceinline__ bool ovf_more(const Params* __restrict__ P, int sel, 
   return true;
 }
 
-template <int NR, int PH, int SP>
+template <int NR, int PH, int SP, int NET = 0>
 __global__ __launch_bounds__(kWave) MJX_PHASE_ATTR void step_phase(const Params* __restrict__ P, int w0, int w1,
                                                     int sel, int last, int integrate,
                                                     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   // the StepFn argument: phase B's Newton row class, phases A and C's integrator switch
-  step_body<NR, PH, SP, false>(S, P, w0, w1, sel, last, PH == 1 ? 0 : integrate,
-                               PH == 1 ? integrate : 0, mask, (int)blockIdx.x);
+  step_body<NR, PH, SP, NET ? 4 : 0>(S, P, w0, w1, sel, last, PH == 1 ? 0 : integrate,
+                                     PH == 1 ? integrate : 0, mask, (int)blockIdx.x);
 }
 // Phase B for the full-capacity row class (the heavy worlds: more constraint rows than the
 // class capacity) and the masked forward.  That launch holds a few hundred worlds on 256 CUs,
@@ -4121,7 +4298,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
 // the latency Newton kernel, phase C back to back per world, hand-offs through the max
 // scratch): an empty list then costs one near-empty launch per substep instead of three.
 // LDS: the largest of the three carves.
-template <int NR, int SP>
+template <int NR, int SP, int NET = 0>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 1))) void step_resolve(
     const Params* __restrict__ P, int w0, int w1, int sel, int last, int integrate,
     const uint8_t* __restrict__ mask) {
@@ -4134,13 +4311,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     }
   }
   for (int bid = (int)blockIdx.x;; bid += (int)gridDim.x) {
-    step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
+    step_body<NR, 0, SP, NET ? 4 : 0>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
     __threadfence();  // the packs this wave stored are read back by the next phase
     __syncthreads();
     step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, 0, /*row_class=*/-1, mask, bid);
     __threadfence();
     __syncthreads();
-    step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
+    step_body<NR, 2, SP, NET ? 4 : 0>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
     if (!ovf_more(P, sel, bid + (int)gridDim.x)) break;
   }
   ovf_clear_on_exit(P, sel);
@@ -4165,20 +4342,20 @@ __device__ __forceinline__ void chain_handoff() {
 }
 template <int NR, int SP, int LAT>
 __global__ __launch_bounds__(kWave)
-__attribute__((amdgpu_waves_per_eu((LAT & 1) ? 1 : (kLean<SP> ? 4 : NR <= 48 ? 3 : 1), (LAT & 1) ? 2 : 8))) void step_chain(
+__attribute__((amdgpu_waves_per_eu((LAT & 1) ? 1 : (LAT & 4) ? (NR <= 48 ? 2 : 1) : (kLean<SP> ? 4 : NR <= 48 ? 3 : 1), (LAT & 1) ? 2 : 8))) void step_chain(
     const Params* __restrict__ P, int w0, int w1, int sel, int last, int integrate,
     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int bid = (int)blockIdx.x;
   const int split = sel & 0xff;
   const int cls1 = (sel >> 8) & 0xff;  // class + 1
-  step_body<NR, 1, SP, LAT>(S, P, w0, w1, split, last, 0, /*row_class=*/cls1 - 1, mask, bid);
+  step_body<NR, 1, SP, LAT & 3>(S, P, w0, w1, split, last, 0, /*row_class=*/cls1 - 1, mask, bid);
   chain_handoff();
-  step_body<NR, 2, SP, 0>(S, P, w0, w1, split | cls1 << 8, last, integrate, 0, mask, bid);
+  step_body<NR, 2, SP, LAT & 4>(S, P, w0, w1, split | cls1 << 8, last, integrate, 0, mask, bid);
   if (sel & kSelChainA) {
     chain_handoff();
-    step_body<NR, 0, SP, 0>(S, P, w0, w1, split | cls1 << 8 | (sel & kSelAPar) | kSelFusedA,
-                                (sel & kSelNextLast) ? 1 : 0, integrate, 0, mask, bid);
+    step_body<NR, 0, SP, LAT & 4>(S, P, w0, w1, split | cls1 << 8 | (sel & kSelAPar) | kSelFusedA,
+                                  (sel & kSelNextLast) ? 1 : 0, integrate, 0, mask, bid);
   }
 }
 
@@ -4187,18 +4364,18 @@ __attribute__((amdgpu_waves_per_eu((LAT & 1) ? 1 : (kLean<SP> ? 4 : NR <= 48 ? 3
 // step_chain.  A workgroup whose world is not masked exits at once.  LDS: the largest of the
 // three max carves.  (Three launches cost two more dispatch ramps and launch gaps on the env
 // step's critical path, for the handful of worlds a step resets.)
-template <int NR, int SP>
+template <int NR, int SP, int NET = 0>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) void step_masked(
     const Params* __restrict__ P, int w0, int w1, int sel, int last, int integrate,
     const uint8_t* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int bid = (int)blockIdx.x;
   if (w0 + bid >= w1 || !mask[w0 + bid]) return;
-  step_body<NR, 0, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
+  step_body<NR, 0, SP, NET ? 4 : 0>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
   chain_handoff();
   step_body<NR, 1, SP, true>(S, P, w0, w1, sel, last, 0, /*row_class=*/-1, mask, bid);
   chain_handoff();
-  step_body<NR, 2, SP, false>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
+  step_body<NR, 2, SP, NET ? 4 : 0>(S, P, w0, w1, sel, last, integrate, 0, mask, bid);
 }
 
 using StepFn = void (*)(const Params*, int, int, int, int, int, const uint8_t*);
@@ -4207,6 +4384,25 @@ using StepFn = void (*)(const Params*, int, int, int, int, int, const uint8_t*);
 template <int NR, int SP>
 StepFn phase_kernel(int ph) {
   constexpr int role = SpecRole<SP>::mask;
+  // the variants whose phases A and C run the actuator networks: generic kernels only (they stand
+  // in for a specialisation's, as for every role a specialisation lacks)
+  if (ph & kPhNet) {
+    if constexpr (SP == 0) {
+      switch (ph & ~kPhNet) {
+        case kPhA: return step_phase<NR, 0, SP, 1>;
+        case kPhC: return step_phase<NR, 2, SP, 1>;
+        case kPhOvfNextA: return step_ovf<NR, 0, SP, 4>;
+        case kPhResolve: return step_resolve<NR, SP, 1>;
+        case kPhChain: return step_chain<NR, SP, 4>;
+        case kPhChainLat: return step_chain<NR, SP, 5>;
+        case kPhMasked: return step_masked<NR, SP, 1>;
+        case kPhChainLatJG: return step_chain<NR, SP, 7>;
+        default: return nullptr;
+      }
+    } else {
+      return nullptr;
+    }
+  }
   switch (ph) {
     case kPhA: return step_phase<NR, 0, SP>;
     case kPhC: return step_phase<NR, 2, SP>;

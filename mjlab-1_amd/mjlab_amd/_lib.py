@@ -22,6 +22,7 @@ EXPORTS = ("mjx_last_error", "mjx_abi_version", "mjx_model_desc_size", "mjx_mode
            "mjx_forward_masked", "mjx_sim_track_air_time", "mjx_marker", "mjx_sim_create_ex",
            "mjx_sim_info", "mjx_sim_mass_matrix", "mjx_spec_register", "mjx_launch_counts",
            "mjx_launch_counts_reset", "mjx_sim_set_actuators", "mjx_actuator_desc_size",
+           "mjx_sim_set_actuator_nets", "mjx_actuator_net_desc_size",
            # include/mjx355_task.h (fused velocity-task managers; bound in fused.py)
            "mjx_task_create", "mjx_task_destroy", "mjx_task_action", "mjx_task_substep",
            "mjx_task_post", "mjx_task_reset", "mjx_task_observe", "mjx_task_desc_size",
@@ -88,6 +89,9 @@ def lib() -> ctypes.CDLL:
   if hasattr(L, "mjx_sim_set_actuators"):
     L.mjx_sim_set_actuators.argtypes = [vp, vp, vp]
     L.mjx_actuator_desc_size.restype = ctypes.c_size_t
+  if hasattr(L, "mjx_sim_set_actuator_nets"):
+    L.mjx_sim_set_actuator_nets.argtypes = [vp, vp, vp]
+    L.mjx_actuator_net_desc_size.restype = ctypes.c_size_t
   missing = [n for n in EXPORTS if not hasattr(L, n)]
   if missing and not os.environ.get("MJX355_LIB"):  # MJX355_LIB: A/B against an older build
     raise MjxError(f"{LIB_PATH} lacks {missing}: rebuild it (make -C mjlab-1_amd/csrc)")
@@ -97,7 +101,7 @@ def lib() -> ctypes.CDLL:
     if name.startswith(("mjx_task_", "mjx_track_")):
       continue  # bound by mjlab_amd.fused / mjlab_amd.fused_tracking
     if name not in ("mjx_last_error", "mjx_field_name", "mjx_model_desc_size",
-                    "mjx_actuator_desc_size"):
+                    "mjx_actuator_desc_size", "mjx_actuator_net_desc_size"):
       getattr(L, name).restype = ci
   from ._capi import ABI_VERSION
   if L.mjx_abi_version() != ABI_VERSION:

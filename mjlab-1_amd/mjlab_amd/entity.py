@@ -18,7 +18,7 @@ from typing import Callable
 import numpy as np
 
 from .actuator import (ActuatorCfg, DcMotorActuatorCfg, DelayedActuatorCfg,  # noqa: F401
-                       IdealPdActuatorCfg)
+                       IdealPdActuatorCfg, LearnedMlpActuator, LearnedMlpActuatorCfg)
 from .compiler.model import (ActuatorSpec, CollisionEdit, EntitySpec, MotorActuatorGroup,
                              PositionActuatorGroup, VelocityActuatorGroup)
 from .spec import Spec, auto_wrap_fixed_base_mocap, mjtJoint

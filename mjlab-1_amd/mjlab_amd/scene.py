@@ -452,8 +452,8 @@ class Entity:
   def write_data_to_sim(self, mask=None):
     """BuiltinActuatorGroup.apply_controls: ctrl[:, ctrl_ids] = target[:, joint_ids]; then
     every explicit actuator's torque from the targets and the joint state
-    (`entity.py:815-825`).  `mask`: the rows whose explicit actuators are evaluated -- a delayed
-    actuator steps only those (the sync-free env's post-reset write passes its reset mask;
+    (`entity.py:815-825`).  `mask`: the rows whose explicit actuators are evaluated -- an actuator
+    with state (`takes_mask`: the delay wrapper, the learned actuator) steps only those (the sync-free env's post-reset write passes its reset mask;
     see `DelayedActuator.compute`)."""
     if self._engine_actuators is not None:
       self._engine_actuators.write_targets(self)
@@ -466,7 +466,7 @@ class Entity:
         self._data.joint_pos_target[:, self._act_joint_local_t]
     if not self._custom_actuators:
       return
-    from .actuator import ActuatorCmd, DelayedActuator
+    from .actuator import ActuatorCmd
     d = self._data
     for k, act in enumerate(self._custom_actuators):
       j = act.joint_ids
@@ -479,7 +479,7 @@ class Entity:
         continue
       # masked: the other rows keep their ctrl (as the engine's masked forward leaves it)
       m = mask.bool()
-      ctrl = act.compute(cmd, mask=m) if isinstance(act, DelayedActuator) else act.compute(cmd)
+      ctrl = act.compute(cmd, mask=m) if getattr(act, "takes_mask", False) else act.compute(cmd)
       d.data.ctrl[:, self._custom_ctrl_cols[k]] = torch.where(m.unsqueeze(1), ctrl, held[k])
 
   def update(self, dt: float):

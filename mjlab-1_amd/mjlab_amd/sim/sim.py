@@ -447,16 +447,21 @@ class Simulation:
     `write_data_to_sim()` + `step(1)`, and `Entity.write_data_to_sim` copies targets only.
     Raises ValueError for an actuator the engine cannot run (`actuator.engine_unsupported`).
     `seed` seeds the lag draws of delayed actuators.  Returns the binding."""
-    from ..actuator import ActuatorDesc, EngineActuators
+    from ..actuator import ActuatorDesc, ActuatorNetDesc, EngineActuators
     L = lib()
     if L.mjx_actuator_desc_size() != ctypes.sizeof(ActuatorDesc):
       raise MjxError("mjxActuatorDesc layout mismatch between include/mjx355.h and actuator.py")
+    if L.mjx_actuator_net_desc_size() != ctypes.sizeof(ActuatorNetDesc):
+      raise MjxError("mjxActuatorNetDesc layout mismatch between include/mjx355.h and actuator.py")
     self.clear_explicit_actuators()
     eng = EngineActuators(self, entities, seed)
+    stream = _stream_handle(self._torch_device)
     try:
-      check(L.mjx_sim_set_actuators(self._sim, ctypes.addressof(eng.desc),
-                                    _stream_handle(self._torch_device)))
+      check(L.mjx_sim_set_actuators(self._sim, ctypes.addressof(eng.desc), stream))
+      if eng.net_desc is not None:  # the learned actuators' networks, after their kinds
+        check(L.mjx_sim_set_actuator_nets(self._sim, ctypes.addressof(eng.net_desc), stream))
     except MjxError:
+      L.mjx_sim_set_actuators(self._sim, None, stream)
       eng.release()
       raise
     self._explicit_actuators = eng
