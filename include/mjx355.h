@@ -40,10 +40,23 @@ enum { MJX_JNT_FREE = 0, MJX_JNT_BALL = 1, MJX_JNT_SLIDE = 2, MJX_JNT_HINGE = 3 
 /* sensor types (subset of mjtSensor used by mjlab tasks) */
 enum { MJX_SENS_GYRO = 0, MJX_SENS_VELOCIMETER = 1, MJX_SENS_ACCELEROMETER = 2,
        MJX_SENS_SUBTREEANGMOM = 3, MJX_SENS_CONTACT = 4, MJX_SENS_FRAMEPOS = 5,
-       MJX_SENS_FRAMEQUAT = 6, MJX_SENS_JOINTPOS = 7, MJX_SENS_JOINTVEL = 8 };
-/* object types for sensors */
+       MJX_SENS_FRAMEQUAT = 6, MJX_SENS_JOINTPOS = 7, MJX_SENS_JOINTVEL = 8,
+       /* Extended sensors: evaluated after the step by one small kernel of their own
+        * (csrc/sensor_ext.hip) from the fields the step stores, as is every MJX_SENS_FRAMEQUAT,
+        * every sensor with a ref frame and the cutoff of any sensor.  Frame sensors take the
+        * object types BODY (the inertial frame: xipos, ximat), XBODY (xpos, xmat), GEOM and SITE,
+        * for the object and for the optional ref frame (sensor_reftype / sensor_refid; reftype
+        * MJX_OBJ_NONE: the world).  MJX_SENS_FRAMEPOS above stays the step kernels' own: site_xpos
+        * of a SITE, xpos of a BODY or XBODY, no ref; MJX_SENS_FRAMEPOSX is the frame position of
+        * any object type (BODY: xipos), with or without a ref. */
+       MJX_SENS_FRAMEPOSX = 9, MJX_SENS_FRAMEXAXIS = 10, MJX_SENS_FRAMEYAXIS = 11,
+       MJX_SENS_FRAMEZAXIS = 12, MJX_SENS_FRAMELINVEL = 13, MJX_SENS_FRAMEANGVEL = 14,
+       MJX_SENS_FRAMELINACC = 15, MJX_SENS_FRAMEANGACC = 16, MJX_SENS_SUBTREECOM = 17,
+       MJX_SENS_SUBTREELINVEL = 18, MJX_SENS_ACTUATORPOS = 19, MJX_SENS_ACTUATORVEL = 20,
+       MJX_SENS_ACTUATORFRC = 21, MJX_SENS_JOINTACTUATORFRC = 22, MJX_SENS_COUNT = 23 };
+/* object types for sensors (mjtObj numbering) */
 enum { MJX_OBJ_NONE = 0, MJX_OBJ_BODY = 1, MJX_OBJ_XBODY = 2, MJX_OBJ_JOINT = 3,
-       MJX_OBJ_GEOM = 5, MJX_OBJ_SITE = 6 };
+       MJX_OBJ_GEOM = 5, MJX_OBJ_SITE = 6, MJX_OBJ_ACTUATOR = 19 };
 /* contact sensor reduce modes (sensor/contact_sensor.py:39-44) */
 enum { MJX_REDUCE_NONE = 0, MJX_REDUCE_MINDIST = 1, MJX_REDUCE_MAXFORCE = 2,
        MJX_REDUCE_NETFORCE = 3 };
@@ -104,6 +117,10 @@ typedef struct mjxModelDesc_ {
   /* heightfields */
   const int32_t *hfield_nrow, *hfield_ncol, *hfield_adr;
   const double *hfield_size /*4*/, *hfield_data /* nhfielddata, normalised [0,1] */;
+  /* sensors, continued (appended: the fields above keep their offsets): cutoff > 0 clamps the
+   * entries of a real-valued sensor to [-cutoff, cutoff]; quaternion and axis sensors and
+   * contact sensors are never clamped */
+  const double* sensor_cutoff;
 } mjxModelDesc;
 
 size_t mjx_model_desc_size(void); /* sizeof(mjxModelDesc): ABI check for FFI bindings */
@@ -315,6 +332,13 @@ int mjx_marker(int tag, void* stream);
  * reference counterpart. */
 int mjx_launch_counts(int64_t* out, int n);
 int mjx_launch_counts_reset(void);
+/* Diagnostics (host side only): launches of the extended-sensor kernel (MJX_SENS_FRAMEPOSX and
+ * later, MJX_SENS_FRAMEQUAT, ref frames, cutoffs) this process has issued, written to out[0];
+ * counted apart from mjx_launch_counts, whose layout is fixed, and cleared with them by
+ * mjx_launch_counts_reset.  A model without extended sensors launches none; one with them
+ * launches one per mjx_step / mjx_forward / mjx_forward_masked.  Returns 0, or -1 for a null
+ * `out`.  No reference counterpart. */
+int mjx_sensor_launch_count(int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,7 @@ struct mjxModel_ {
   // static world frames of heightfield geoms (terrain bodies are welded to the world)
   std::vector<int> static_geoms;
   std::vector<float> static_xpos, static_xmat;
+  mjx::SensorExt ext;  // extended sensors (sensor_ext.hip); n = 0: the kernel is never launched
 };
 
 struct mjxSim_ {
@@ -219,6 +220,74 @@ static int sync_params(mjxSim_* s, void* stream) {
   return 0;
 }
 
+// The extended-sensor table of a descriptor (engine.h SensorExtRec), sorted by kind, every id
+// checked against the model's sizes: a bad id is an error here, not a device fault.  Host
+// work only (it precedes all device work of mjx_model_create).  Returns "" or the error.
+static std::string build_sensor_ext(const mjxModelDesc* desc, std::vector<mjx::SensorExtRec>& out) {
+  using namespace mjx;
+  auto frame_ok = [&](int type, int id) {
+    const int n = type == OBJ_BODY || type == OBJ_XBODY ? desc->nbody
+                  : type == OBJ_GEOM ? desc->ngeom : type == OBJ_SITE ? desc->nsite : -1;
+    return id >= 0 && id < n;
+  };
+  auto frame_body = [&](int type, int id) {
+    return type == OBJ_GEOM ? desc->geom_bodyid[id] : type == OBJ_SITE ? desc->site_bodyid[id] : id;
+  };
+  for (int s = 0; s < desc->nsensor; s++) {
+    const int type = desc->sensor_type[s], ot = desc->sensor_objtype[s], oi = desc->sensor_objid[s];
+    const int rt = desc->sensor_reftype[s], ri = desc->sensor_refid[s];
+    const int adr = desc->sensor_adr[s], dim = desc->sensor_dim[s];
+    const float cutoff = (float)desc->sensor_cutoff[s];
+    const std::string who = "sensor " + std::to_string(s) + ": ";
+    if (type < 0 || type >= SENS_COUNT) return who + "unknown sensor type " + std::to_string(type);
+    if (adr < 0 || dim < 0 || adr + dim > desc->nsensordata) return who + "sensordata range out of bounds";
+    if (type == SENS_CONTACT) continue;
+    const bool frame = type == SENS_FRAMEQUAT || (type >= SENS_FRAMEPOSX && type <= SENS_FRAMEANGACC);
+    if (type == SENS_FRAMEPOS && rt != OBJ_NONE)
+      return who + "MJX_SENS_FRAMEPOS takes no ref frame (MJX_SENS_FRAMEPOSX does)";
+    SensorExtRec r{};
+    r.kind = type; r.adr = adr; r.dim = dim; r.cutoff = cutoff > 0.f ? cutoff : 0.f;
+    r.otype = ot; r.oid = oi; r.rtype = OBJ_NONE;
+    if (frame) {
+      if (dim != (type == SENS_FRAMEQUAT ? 4 : 3)) return who + "frame sensor dimension";
+      if (!frame_ok(ot, oi)) return who + "object type or id out of range";
+      r.obody = frame_body(ot, oi);
+      if (r.obody < 0 || r.obody >= desc->nbody) return who + "object body id out of range";
+      r.oroot = desc->body_rootid[r.obody];
+      if (rt != OBJ_NONE) {
+        if (type == SENS_FRAMELINACC || type == SENS_FRAMEANGACC)
+          return who + "framelinacc / frameangacc take no ref frame";
+        if (!frame_ok(rt, ri)) return who + "ref type or id out of range";
+        r.rtype = rt; r.rid = ri; r.rbody = frame_body(rt, ri);
+        if (r.rbody < 0 || r.rbody >= desc->nbody) return who + "ref body id out of range";
+        r.rroot = desc->body_rootid[r.rbody];
+        if (r.rroot < 0 || r.rroot >= desc->nbody) return who + "ref root id out of range";
+      }
+      if (r.oroot < 0 || r.oroot >= desc->nbody) return who + "object root id out of range";
+      if (type == SENS_FRAMEQUAT || (type >= SENS_FRAMEXAXIS && type <= SENS_FRAMEZAXIS)) r.cutoff = 0.f;
+    } else if (type >= SENS_SUBTREECOM) {
+      const bool body = type == SENS_SUBTREECOM || type == SENS_SUBTREELINVEL;
+      const int n = body ? desc->nbody : type == SENS_JOINTACTUATORFRC ? desc->njnt : desc->nu;
+      if (oi < 0 || oi >= n) return who + "object id out of range";
+      if (dim != (body ? 3 : 1)) return who + "sensor dimension";
+      if (type == SENS_JOINTACTUATORFRC) {
+        const int jt = desc->jnt_type[oi];
+        if (jt != JNT_HINGE && jt != JNT_SLIDE) return who + "jointactuatorfrc takes a hinge or slide joint";
+        r.oid = desc->jnt_dofadr[oi];  // the entry of qfrc_actuator
+        if (r.oid < 0 || r.oid >= desc->nv) return who + "joint dof address out of range";
+      }
+    } else {
+      // a kind the step kernels write: listed only for its cutoff
+      if (r.cutoff <= 0.f) continue;
+      r.kind = kSensClamp;
+    }
+    out.push_back(r);
+  }
+  std::stable_sort(out.begin(), out.end(),
+                   [](const SensorExtRec& a, const SensorExtRec& b) { return a.kind < b.kind; });
+  return "";
+}
+
 extern "C" {
 
 const char* mjx_last_error(void) { return g_err.c_str(); }
@@ -255,6 +324,17 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
     return fail("at most 64 actuators and 64 joints per world supported");
   if (desc->cone != 0) return fail("only pyramidal cones are supported");
   if (desc->contact_maxmatch < 1) return fail("contact_maxmatch must be >= 1");
+  // (a host that leaves the appended sensor_cutoff null has no cutoffs)
+  mjxModelDesc with_cutoff = *desc;
+  const std::vector<double> no_cutoff(desc->nsensor > 0 ? desc->nsensor : 1, 0.0);
+  if (!with_cutoff.sensor_cutoff) with_cutoff.sensor_cutoff = no_cutoff.data();
+  desc = &with_cutoff;
+  std::vector<mjx::SensorExtRec> ext;
+  {
+    const std::string err = build_sensor_ext(desc, ext);
+    if (!err.empty()) return fail(err);
+    if (ext.size() > 65535) return fail("at most 65535 extended sensors (one grid row each)");
+  }
   HIPCHK(hipSetDevice(device));
   auto* m = new mjxModel_();
   m->device = device;
@@ -575,6 +655,11 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
     if (upload(g2.data(), sizeof(uint64_t) * g2.size(), &p)) { delete m; return -1; }
     m->dm.geom_csmask2 = (const uint64_t*)p;
   }
+  if (!ext.empty()) {
+    if (upload(ext.data(), sizeof(mjx::SensorExtRec) * ext.size(), &p)) { delete m; return -1; }
+    m->ext.rec = (const mjx::SensorExtRec*)p;
+    m->ext.n = (int)ext.size();
+  }
   *out = m;
   return 0;
 }
@@ -837,7 +922,7 @@ int mjx_step(mjxSim* s, int nsubstep, void* stream) {
   const mjx::Params hb = s->big ? host_params_big(s) : mjx::Params{};
   hipError_t e = mjx::launch_step(host_params(s), s->dparams, s->nworld, nsubstep, 1, nullptr,
                                   (hipStream_t)stream, &s->side, s->big ? &hb : nullptr,
-                                  s->dparams_big);
+                                  s->dparams_big, &s->model->ext);
   if (e != hipSuccess) return fail(std::string("step launch: ") + hipGetErrorString(e));
   return 0;
 }
@@ -849,7 +934,7 @@ int mjx_forward_masked(mjxSim* s, const uint8_t* mask, void* stream) {
   const mjx::Params hb = s->big ? host_params_big(s) : mjx::Params{};
   hipError_t e = mjx::launch_step(host_params(s), s->dparams, s->nworld, 1, 0, mask,
                                   (hipStream_t)stream, &s->side, s->big ? &hb : nullptr,
-                                  s->dparams_big);
+                                  s->dparams_big, &s->model->ext);
   if (e != hipSuccess) return fail(std::string("forward launch: ") + hipGetErrorString(e));
   return 0;
 }
@@ -1221,6 +1306,13 @@ int mjx_launch_counts(int64_t* out, int n) {
 
 int mjx_launch_counts_reset(void) {
   mjx::launch_counts_reset();
+  mjx::sensor_ext_launches_reset();
+  return 0;
+}
+
+int mjx_sensor_launch_count(int64_t* out) {
+  if (!out) return fail("mjx_sensor_launch_count: null output");
+  out[0] = (int64_t)mjx::sensor_ext_launches();
   return 0;
 }
 

@@ -30,8 +30,14 @@ enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
 enum { SENS_GYRO = 0, SENS_VELOCIMETER = 1, SENS_ACCELEROMETER = 2, SENS_SUBTREEANGMOM = 3,
        SENS_CONTACT = 4, SENS_FRAMEPOS = 5, SENS_FRAMEQUAT = 6, SENS_JOINTPOS = 7,
-       SENS_JOINTVEL = 8 };
-enum { OBJ_SITE = 6 };
+       SENS_JOINTVEL = 8,
+       // extended sensors (sensor_ext.hip; include/mjx355.h): the step kernels skip them
+       SENS_FRAMEPOSX = 9, SENS_FRAMEXAXIS = 10, SENS_FRAMEYAXIS = 11, SENS_FRAMEZAXIS = 12,
+       SENS_FRAMELINVEL = 13, SENS_FRAMEANGVEL = 14, SENS_FRAMELINACC = 15, SENS_FRAMEANGACC = 16,
+       SENS_SUBTREECOM = 17, SENS_SUBTREELINVEL = 18, SENS_ACTUATORPOS = 19, SENS_ACTUATORVEL = 20,
+       SENS_ACTUATORFRC = 21, SENS_JOINTACTUATORFRC = 22, SENS_COUNT = 23 };
+enum { OBJ_NONE = 0, OBJ_BODY = 1, OBJ_XBODY = 2, OBJ_JOINT = 3, OBJ_GEOM = 5, OBJ_SITE = 6,
+       OBJ_ACTUATOR = 19 };
 enum { REDUCE_NONE = 0, REDUCE_MINDIST = 1, REDUCE_MAXFORCE = 2, REDUCE_NETFORCE = 3 };
 
 struct Dims {
@@ -296,6 +302,29 @@ constexpr int kSelFusedA = 1 << 22;
 // priority (s_setprio) over the bulk-class waves sharing their SIMDs
 constexpr int kSelPrio = 1 << 23;
 
+// Extended sensors (sensor_ext.hip): one host-built record per sensor the step kernels do not
+// finish -- a kind of SENS_FRAMEPOSX or later, any SENS_FRAMEQUAT, a ref frame, or a cutoff on
+// a kind the step kernels write (kind = kSensClamp: clamp what they wrote).  Records are sorted
+// by kind; ids are validated against the model's sizes by mjx_model_create.
+constexpr int kSensClamp = -1;
+struct SensorExtRec {
+  int kind;        // SENS_* or kSensClamp
+  int adr, dim;    // sensordata entries [adr, adr + dim)
+  float cutoff;    // > 0: clamp the entries to [-cutoff, cutoff] (never a quaternion or an axis)
+  int otype, oid;  // frame kinds: OBJ_* and id of the object; others: the id to copy from
+  int obody;       // body the object frame is attached to
+  int oroot;       // body_rootid[obody]: the subtree_com the body's cvel / cacc refer to
+  int rtype, rid, rbody, rroot;  // the ref frame likewise; rtype OBJ_NONE: the world
+};
+struct SensorExt {
+  const SensorExtRec* rec = nullptr;  // device
+  int n = 0;
+};
+hipError_t launch_sensor_ext(const struct Params* dev, const SensorExt& ext, int nworld,
+                             const uint8_t* mask, hipStream_t stream);
+long long sensor_ext_launches();
+void sensor_ext_launches_reset();
+
 // Launchers (enqueue on `stream`; never synchronise).  `dev` points to a device copy of
 // `host`; `host` is used only for the launch geometry.
 hipError_t prepare_step(const Params& host);  // one-time kernel attributes (not capturable)
@@ -326,7 +355,7 @@ bool range_chain_default(const struct Params& host, int nworld, int nsplit);
 hipError_t launch_step(const Params& host, const Params* dev, int nworld, int nsubstep,
                        int integrate, const uint8_t* mask, hipStream_t stream,
                        const SideStream* side, const Params* hbig = nullptr,
-                       const Params* dbig = nullptr);
+                       const Params* dbig = nullptr, const SensorExt* ext = nullptr);
 // Newton row classes (capacities ascending into caps[]); returns how many are used.
 int choose_row_classes(const Dims& d, int spec, int (&caps)[kRowClasses]);
 hipError_t launch_reset(const Dims& d, const DModel& m, const DData& dd, const uint8_t* mask,

@@ -581,9 +581,9 @@ static hipError_t substep_flat(const StepCtx& c, const Range& r) {
   return forked ? ovf_join(c, r) : hipSuccess;
 }
 
-hipError_t launch_step(const Params& host, const Params* dev, int nworld, int nsubstep,
-                       int integrate, const uint8_t* mask, hipStream_t stream,
-                       const SideStream* side, const Params* hbig, const Params* dbig) {
+static hipError_t launch_phases(const Params& host, const Params* dev, int nworld, int nsubstep,
+                                int integrate, const uint8_t* mask, hipStream_t stream,
+                                const SideStream* side, const Params* hbig, const Params* dbig) {
   if (nworld <= 0) return hipSuccess;
   const LaunchKnobs& kn = knobs();
   const int nc = host.nrowclass;
@@ -618,6 +618,18 @@ hipError_t launch_step(const Params& host, const Params* dev, int nworld, int ns
   }
   if ((e = join_splits(s, side, 0)) != hipSuccess) return e;
   return hipGetLastError();
+}
+
+// The step's launches, then -- on the launch stream, behind the last join -- the extended
+// sensors of a model that has any (sensor_ext.hip): they read what the last substep stored.
+hipError_t launch_step(const Params& host, const Params* dev, int nworld, int nsubstep,
+                       int integrate, const uint8_t* mask, hipStream_t stream,
+                       const SideStream* side, const Params* hbig, const Params* dbig,
+                       const SensorExt* ext) {
+  const hipError_t e = launch_phases(host, dev, nworld, nsubstep, integrate, mask, stream, side,
+                                     hbig, dbig);
+  if (e != hipSuccess || !ext || ext->n <= 0 || nworld <= 0) return e;
+  return launch_sensor_ext(dev, *ext, nworld, mask, stream);
 }
 
 // One-wave workgroups resident per CU at `bytes` of dynamic LDS, as measured on MI355X

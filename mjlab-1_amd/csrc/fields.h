@@ -45,7 +45,8 @@
   X(geom_rbound, d.ngeom, 1) X(site_pos, d.nsite, 3) X(site_quat, d.nsite, 4)        \
   X(actuator_gear, d.nu, 1) X(actuator_gainprm, d.nu, 3) X(actuator_biasprm, d.nu, 3) \
   X(actuator_forcerange, d.nu, 2) X(actuator_ctrlrange, d.nu, 2)                     \
-  X(hfield_size, d.nhfield, 4) X(hfield_data, d.nhfielddata, 1)
+  X(hfield_size, d.nhfield, 4) X(hfield_data, d.nhfielddata, 1)                      \
+  X(sensor_cutoff, d.nsensor, 1)
 
 // Per-world data fields, fp32, layout [nworld][count*width] (torch row-major).
 #define MJX_DATA_FLOAT_FIELDS(X)                                                       \

@@ -51,6 +51,7 @@ _ARRAYS = (
   + [("pair_geom1", _I), ("pair_geom2", _I)]
   + [(n, _I) for n in ("hfield_nrow", "hfield_ncol", "hfield_adr")]
   + [("hfield_size", _D), ("hfield_data", _D)]
+  + [("sensor_cutoff", _D)]
 )
 
 
@@ -61,6 +62,12 @@ class ModelDesc(ctypes.Structure):
 
 
 _DTYPES = {_I: np.int32, _D: np.float64, _U64: np.uint64, _U32: np.uint32}
+
+
+def sensor_cutoff(model) -> np.ndarray:
+  """The model's sensor cutoffs; a model compiled without any (every shipped scene) carries no
+  such array and reads as zeros."""
+  return np.asarray(model.arrays.get("sensor_cutoff", np.zeros(int(model.nsensor))), np.float64)
 
 
 def make_desc(model) -> tuple[ModelDesc, list]:
@@ -83,7 +90,8 @@ def make_desc(model) -> tuple[ModelDesc, list]:
     d.gravity[i] = float(model.gravity[i])
   keep = []
   for name, ct in _ARRAYS:
-    arr = np.ascontiguousarray(np.asarray(model.arrays[name]).reshape(-1), dtype=_DTYPES[ct])
+    src = model.arrays[name] if name != "sensor_cutoff" else sensor_cutoff(model)
+    arr = np.ascontiguousarray(np.asarray(src).reshape(-1), dtype=_DTYPES[ct])
     if arr.size == 0:
       arr = np.zeros(1, dtype=_DTYPES[ct])
     keep.append(arr)

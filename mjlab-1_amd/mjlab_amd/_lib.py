@@ -22,7 +22,7 @@ EXPORTS = ("mjx_last_error", "mjx_abi_version", "mjx_model_desc_size", "mjx_mode
            "mjx_forward_masked", "mjx_sim_track_air_time", "mjx_marker", "mjx_sim_create_ex",
            "mjx_sim_info", "mjx_sim_mass_matrix", "mjx_spec_register", "mjx_launch_counts",
            "mjx_launch_counts_reset", "mjx_sim_set_actuators", "mjx_actuator_desc_size",
-           "mjx_sim_set_actuator_nets", "mjx_actuator_net_desc_size",
+           "mjx_sim_set_actuator_nets", "mjx_actuator_net_desc_size", "mjx_sensor_launch_count",
            # include/mjx355_task.h (fused velocity-task managers; bound in fused.py)
            "mjx_task_create", "mjx_task_destroy", "mjx_task_action", "mjx_task_substep",
            "mjx_task_post", "mjx_task_reset", "mjx_task_observe", "mjx_task_desc_size",
@@ -80,6 +80,8 @@ def lib() -> ctypes.CDLL:
   if hasattr(L, "mjx_launch_counts"):  # absent from an older engine build (MJX355_LIB)
     L.mjx_launch_counts.argtypes = [ctypes.POINTER(ctypes.c_int64), ci]
     L.mjx_launch_counts_reset.argtypes = []
+  if hasattr(L, "mjx_sensor_launch_count"):
+    L.mjx_sensor_launch_count.argtypes = [ctypes.POINTER(ctypes.c_int64)]
   if hasattr(L, "mjx_terrain_levels"):
     f32, u64 = ctypes.c_float, ctypes.c_uint64
     L.mjx_terrain_levels.argtypes = [ci, vp, vp, ci, ci, vp, f32, f32, vp, vp, vp, ci, ci, vp, u64,

@@ -6,7 +6,9 @@ This is the setup path that the reference delegates to MuJoCo's `MjSpec.from_fil
 supported: nested `<default>` classes and `childclass`, bodies with
 `<inertial>`, free/hinge/slide/ball joints, primitive geoms (plane, sphere,
 capsule, box, hfield placeholder) with `fromto`, sites, `<contact><exclude>` and
-the sensors gyro / velocimeter / accelerometer / subtreeangmom.
+`<sensor>` elements, kept as (tag, attributes) for the scene compiler (`compiler/model.py`
+`push_builtin`: the site, joint, subtree, actuator and frame sensors with MuJoCo's `objtype` /
+`objname` / `reftype` / `refname` / `cutoff` attributes).
 
 Visual mesh geoms are kept as frames (they have no physics effect) and their
 mesh files are never opened, so a missing STL (the Go1 `trunk.stl`,

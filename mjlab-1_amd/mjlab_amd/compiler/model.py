@@ -38,6 +38,45 @@ _SENSOR_DIM = {SENS_GYRO: 3, SENS_VELOCIMETER: 3, SENS_ACCELEROMETER: 3,
                SENS_SUBTREEANGMOM: 3, SENS_FRAMEPOS: 3, SENS_FRAMEQUAT: 4,
                SENS_JOINTPOS: 1, SENS_JOINTVEL: 1}
 OBJ_BODY, OBJ_XBODY, OBJ_GEOM, OBJ_SITE, OBJ_JOINT, OBJ_NONE = 1, 2, 5, 6, 3, 0
+OBJ_ACTUATOR = 19
+# Extended sensors (include/mjx355.h): evaluated by the engine's sensor kernel after the step.
+# SENS_FRAMEPOSX is a framepos the step kernels do not evaluate (a geom or inertial frame, or
+# any frame relative to a ref); SENS_FRAMEPOS stays the step kernels' own (site / xbody, no ref).
+(SENS_FRAMEPOSX, SENS_FRAMEXAXIS, SENS_FRAMEYAXIS, SENS_FRAMEZAXIS, SENS_FRAMELINVEL,
+ SENS_FRAMEANGVEL, SENS_FRAMELINACC, SENS_FRAMEANGACC, SENS_SUBTREECOM, SENS_SUBTREELINVEL,
+ SENS_ACTUATORPOS, SENS_ACTUATORVEL, SENS_ACTUATORFRC, SENS_JOINTACTUATORFRC) = range(9, 23)
+_SENSOR_TAGS.update(framexaxis=SENS_FRAMEXAXIS, frameyaxis=SENS_FRAMEYAXIS,
+                    framezaxis=SENS_FRAMEZAXIS, framelinvel=SENS_FRAMELINVEL,
+                    frameangvel=SENS_FRAMEANGVEL, framelinacc=SENS_FRAMELINACC,
+                    frameangacc=SENS_FRAMEANGACC, subtreecom=SENS_SUBTREECOM,
+                    subtreelinvel=SENS_SUBTREELINVEL, actuatorpos=SENS_ACTUATORPOS,
+                    actuatorvel=SENS_ACTUATORVEL, actuatorfrc=SENS_ACTUATORFRC,
+                    jointactuatorfrc=SENS_JOINTACTUATORFRC)
+_SENSOR_DIM.update({t: 3 for t in range(SENS_FRAMEPOSX, SENS_SUBTREELINVEL + 1)})
+_SENSOR_DIM.update({t: 1 for t in range(SENS_ACTUATORPOS, SENS_JOINTACTUATORFRC + 1)})
+FRAME_SENSORS = ("framepos", "framequat", "framexaxis", "frameyaxis", "framezaxis", "framelinvel",
+                 "frameangvel", "framelinacc", "frameangacc")
+_FRAME_OBJ = {"body": OBJ_BODY, "xbody": OBJ_XBODY, "geom": OBJ_GEOM, "site": OBJ_SITE}
+# object type each remaining sensor takes
+_SENSOR_OBJ = {"gyro": "site", "velocimeter": "site", "accelerometer": "site",
+               "subtreeangmom": "body", "subtreecom": "body", "subtreelinvel": "body",
+               "jointpos": "joint", "jointvel": "joint", "jointactuatorfrc": "joint",
+               "actuatorpos": "actuator", "actuatorvel": "actuator", "actuatorfrc": "actuator"}
+# sensor kinds the engine does not evaluate, and why
+_PRE = "needs the state before integration ({}), which is not in memory after a step"
+_FRC = "needs {}, which the engine does not store"
+REFUSED_SENSORS = {
+  "jointlimitpos": _PRE.format("qpos"), "jointlimitvel": _PRE.format("qvel"),
+  "clock": _PRE.format("time"),
+  "jointlimitfrc": _FRC.format("the limit rows' constraint forces"),
+  "force": _FRC.format("the interaction forces between bodies (cfrc_int)"),
+  "torque": _FRC.format("the interaction forces between bodies (cfrc_int)"),
+  "magnetometer": "the model has no magnetic field option",
+  "rangefinder": "the engine casts no rays",
+  "tendonpos": "the compiler has no tendons", "tendonvel": "the compiler has no tendons",
+  "tendonactuatorfrc": "the compiler has no tendons",
+  "e_potential": "the engine does not compute energies",
+  "e_kinetic": "the engine does not compute energies"}
 CONTACT_FIELD_DIM = {"found": 1, "force": 3, "torque": 3, "dist": 1, "pos": 3, "normal": 3,
                      "tangent": 3}
 CONTACT_FIELD_BIT = {"found": 0, "force": 1, "torque": 2, "dist": 3, "pos": 4, "normal": 5,
@@ -134,10 +173,14 @@ class ContactSensorSpec:
 class BuiltinSensorSpec:
   """A builtin sensor added by the scene config (`sensor/builtin_sensor.py:279-305`): MJCF tag
   (gyro, accelerometer, jointpos, ...), its object attribute ({"site" | "body" | "joint":
-  prefixed name}) and the sensor's full name."""
+  prefixed name}, or MuJoCo's {"objtype", "objname"}) and the sensor's full name; `ref`: the
+  frame a frame sensor is expressed in, (type, prefixed name), None: the world; `cutoff` > 0
+  clamps a real-valued sensor's entries to [-cutoff, cutoff]."""
   tag: str
   attrs: dict
   name: str
+  ref: tuple | None = None
+  cutoff: float = 0.0
 
 
 @dataclass
@@ -484,7 +527,7 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
     for (b1, b2) in xml.excludes:
       excludes.append((prefix + b1, prefix + b2))
     for tag, attrs in xml.sensors:
-      xml_sensors.append((tag, {k: (prefix + v if k in ("site", "body", "joint", "objname")
+      xml_sensors.append((tag, {k: (prefix + v if k in SENSOR_NAME_ATTRS and v != "world"
                                     else v) for k, v in attrs.items()},
                           prefix + attrs.get("name", "")))
     # actuators (cfg order, joints in natural order)
@@ -752,33 +795,79 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
 
   # sensors
   stype, sobjtype, sobjid, sreftype, srefid, sadr, sdim, sint = [], [], [], [], [], [], [], []
-  snames = []
+  snames, scut = [], []
   smask1, smask2 = [], []
   adr = 0
   nmw = max(1, (m.ngeom + 31) // 32)  # mask words per sensor (mjxModelDesc.nmaskword)
 
-  def push(t, ot, oi, rt, ri, dim, intprm=(0, 0, 0), name="", mk1=None, mk2=None):
+  def push(t, ot, oi, rt, ri, dim, intprm=(0, 0, 0), name="", mk1=None, mk2=None, cutoff=0.0):
     nonlocal adr
     stype.append(t); sobjtype.append(ot); sobjid.append(oi); sreftype.append(rt)
     srefid.append(ri); sadr.append(adr); sdim.append(dim); sint.append(intprm)
-    snames.append(name)
+    snames.append(name); scut.append(float(cutoff))
     smask1.append(mk1 if mk1 is not None else np.zeros(nmw, np.uint32))
     smask2.append(mk2 if mk2 is not None else np.zeros(nmw, np.uint32))
     adr += dim
 
-  def push_builtin(tag, attrs, name):
+  def frame_id(kind, oname, name):
+    """Index of the named body / geom / site a frame sensor (or its ref) is attached to."""
+    if kind == "camera":
+      raise NotImplementedError(f"sensor '{name}': camera frames (the compiler has no cameras)")
+    if kind not in _FRAME_OBJ:
+      raise ValueError(f"sensor '{name}': a frame is a body, xbody, geom or site, not {kind!r}")
+    names = body_names if kind in ("body", "xbody") else m.names[kind]
+    if oname not in names:
+      raise ValueError(f"sensor '{name}': no {kind} named '{oname}'")
+    return names.index(oname)
+
+  def push_builtin(tag, attrs, name, ref=None, cutoff=0.0):
+    if tag in REFUSED_SENSORS:
+      raise NotImplementedError(f"sensor '{name}': {tag} {REFUSED_SENSORS[tag]}")
     if tag not in _SENSOR_TAGS:
       raise NotImplementedError(f"sensor '{name}': type {tag!r} (supported: {sorted(_SENSOR_TAGS)})")
     t = _SENSOR_TAGS[tag]
-    if "site" in attrs:
-      ot, oi = OBJ_SITE, m.names["site"].index(attrs["site"])
-    elif "body" in attrs:
-      ot, oi = OBJ_BODY, body_names.index(attrs["body"])
-    elif "joint" in attrs:
-      ot, oi = OBJ_JOINT, jname.index(attrs["joint"])
+    cutoff = float(attrs.get("cutoff", cutoff))
+    if "reftype" in attrs or "refname" in attrs:
+      ref = (attrs.get("reftype"), attrs.get("refname"))
+    # the object: MuJoCo's objtype / objname, or the one-attribute forms
+    shorthand = "objtype" not in attrs
+    if not shorthand:
+      kind, oname = attrs["objtype"], attrs.get("objname")
     else:
-      raise ValueError(f"unsupported sensor attrs {attrs}")
-    push(t, ot, oi, OBJ_NONE, -1, _SENSOR_DIM[t], name=name)
+      kind = next((k for k in ("site", "body", "joint", "actuator") if k in attrs), None)
+      if kind is None:
+        raise ValueError(f"unsupported sensor attrs {attrs}")
+      oname = attrs[kind]
+    if tag in FRAME_SENSORS:
+      # <framepos body="..."> has always meant the body's own frame; only objtype="body" is
+      # the inertial frame
+      if shorthand and kind == "body":
+        kind = "xbody"
+      oi = frame_id(kind, oname, name)
+      rt, ri = OBJ_NONE, -1
+      if ref is not None:
+        if tag in ("framelinacc", "frameangacc"):
+          raise NotImplementedError(f"sensor '{name}': {tag} relative to a ref frame")
+        rt, ri = _FRAME_OBJ.get(ref[0]), frame_id(ref[0], ref[1], name)
+      if tag == "framepos" and ref is None and kind in ("site", "xbody"):
+        # the step kernels' own framepos, encoded as it always was
+        push(t, OBJ_SITE if kind == "site" else OBJ_BODY, oi, OBJ_NONE, -1, 3, name=name, cutoff=cutoff)
+        return
+      push(SENS_FRAMEPOSX if tag == "framepos" else t, _FRAME_OBJ[kind], oi, rt, ri, _SENSOR_DIM[t],
+           name=name, cutoff=cutoff)
+      return
+    if ref is not None:
+      raise ValueError(f"sensor '{name}': {tag} does not take a ref frame")
+    if kind != _SENSOR_OBJ[tag]:
+      raise ValueError(f"sensor '{name}': {tag} takes a {_SENSOR_OBJ[tag]}, not a {kind}")
+    names, ot = {"site": (m.names["site"], OBJ_SITE), "body": (body_names, OBJ_BODY),
+                 "joint": (jname, OBJ_JOINT), "actuator": (m.names["actuator"], OBJ_ACTUATOR)}[kind]
+    if oname not in names:
+      raise ValueError(f"sensor '{name}': no {kind} named '{oname}'")
+    oi = names.index(oname)
+    if tag == "jointactuatorfrc" and int(jtype[oi]) not in (JOINT_TYPES["hinge"], JOINT_TYPES["slide"]):
+      raise ValueError(f"sensor '{name}': jointactuatorfrc takes a hinge or slide joint")
+    push(t, ot, oi, OBJ_NONE, -1, _SENSOR_DIM[t], name=name, cutoff=cutoff)
 
   for tag, attrs, name in xml_sensors:
     push_builtin(tag, attrs, name)
@@ -815,7 +904,7 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   objmode = {"geom": OBJ_GEOM, "body": OBJ_BODY, "subtree": OBJ_XBODY}
   for cs in contact_sensors:
     if isinstance(cs, BuiltinSensorSpec):  # scene-config sensors keep the config's order
-      push_builtin(cs.tag, cs.attrs, cs.name)
+      push_builtin(cs.tag, cs.attrs, cs.name, cs.ref, cs.cutoff)
       continue
     for prim in cs.primary_names:
       for fld in cs.fields:
@@ -838,6 +927,8 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   A["sensor_intprm"] = np.array(sint, np.int32).reshape(-1, 3)
   A["sensor_geommask1"] = np.array(smask1, np.uint32).reshape(-1, nmw)
   A["sensor_geommask2"] = np.array(smask2, np.uint32).reshape(-1, nmw)
+  if any(c > 0 for c in scut):  # (a model without cutoffs keeps the arrays it always had)
+    A["sensor_cutoff"] = np.array(scut, float)
   m.names["sensor"] = snames
 
   # keyframe "init_state" (src/mjlab/entity/entity.py:170-207)
@@ -902,6 +993,8 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
 
 
 _GEOM_DEFAULTS_FRICTION = (1.0, 0.005, 0.0001)
+# sensor attributes that name an object: prefixed when an entity is attached
+SENSOR_NAME_ATTRS = ("site", "body", "joint", "actuator", "objname", "refname")
 
 
 # ---------------------------------------------------------------------------- setConst

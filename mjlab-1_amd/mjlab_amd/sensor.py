@@ -13,7 +13,7 @@ import re
 from dataclasses import dataclass
 from typing import Literal
 
-from .compiler.model import BuiltinSensorSpec, ContactSensorSpec
+from .compiler.model import REFUSED_SENSORS, BuiltinSensorSpec, ContactSensorSpec
 
 
 @dataclass
@@ -123,9 +123,12 @@ _REQUIRES_OBJ = {"jointpos": "joint", "jointvel": "joint", "jointlimitpos": "joi
                  "actuatorpos": "actuator", "actuatorvel": "actuator", "actuatorfrc": "actuator"}
 _FRAME_TYPES = {"body", "xbody", "geom", "site", "camera"}
 # what the engine evaluates: sensor type -> the object types it takes
+_ENGINE_FRAMES = {"body", "xbody", "geom", "site"}  # (no cameras in the compiler)
 _ENGINE = {"accelerometer": {"site"}, "velocimeter": {"site"}, "gyro": {"site"},
-           "framepos": {"site", "xbody"}, "framequat": {"site", "xbody"},
-           "jointpos": {"joint"}, "jointvel": {"joint"}, "subtreeangmom": {"body"}}
+           **{st: _ENGINE_FRAMES for st in sorted(_REQUIRES_FRAME)},
+           "jointpos": {"joint"}, "jointvel": {"joint"}, "jointactuatorfrc": {"joint"},
+           "subtreeangmom": {"body"}, "subtreecom": {"body"}, "subtreelinvel": {"body"},
+           "actuatorpos": {"actuator"}, "actuatorvel": {"actuator"}, "actuatorfrc": {"actuator"}}
 
 
 @dataclass
@@ -143,8 +146,9 @@ class ObjRef:
 class BuiltinSensorCfg:
   """`builtin_sensor.py:195-250`: a MuJoCo builtin sensor added by the scene config; the
   name is entity-prefixed when `obj` names an entity.  The object-type rules are checked at
-  construction as the reference does; types the engine does not evaluate raise at scene
-  construction (`expand`)."""
+  construction as the reference does; types the engine does not evaluate (REFUSED_SENSORS,
+  camera frames, a ref on framelinacc / frameangacc) raise at scene construction (`expand`).
+  `obj.type="body"` is the inertial frame and "xbody" the body's own, as in MuJoCo."""
   name: str
   sensor_type: str
   obj: ObjRef | None = None
@@ -182,10 +186,17 @@ class BuiltinSensorCfg:
   def expand(self, entities: dict) -> BuiltinSensorSpec:
     del entities
     st, obj = self.sensor_type, self.obj
+    if st in REFUSED_SENSORS:
+      raise NotImplementedError(f"sensor '{self.name}': {st} {REFUSED_SENSORS[st]}")
     if st not in _ENGINE or obj is None or obj.type not in _ENGINE[st]:
       raise NotImplementedError(f"sensor '{self.name}': {st} on a {obj.type if obj else None} "
                                 f"(the engine evaluates {_ENGINE})")
-    if self.ref is not None or self.cutoff > 0:
-      raise NotImplementedError(f"sensor '{self.name}': ref frames and cutoff")
-    key = {"site": "site", "xbody": "body", "body": "body", "joint": "joint"}[obj.type]
-    return BuiltinSensorSpec(st, {key: obj.prefixed_name()}, self.name)
+    ref = None
+    if self.ref is not None:
+      if st in ("framelinacc", "frameangacc"):
+        raise NotImplementedError(f"sensor '{self.name}': {st} relative to a ref frame")
+      if self.ref.type not in _ENGINE_FRAMES:
+        raise NotImplementedError(f"sensor '{self.name}': a {self.ref.type} ref frame")
+      ref = (self.ref.type, self.ref.prefixed_name())
+    return BuiltinSensorSpec(st, {"objtype": obj.type, "objname": obj.prefixed_name()}, self.name,
+                             ref=ref, cutoff=float(self.cutoff))

@@ -29,7 +29,8 @@ import numpy as np
 
 from .compiler.mjcf import (_GEOM_DEFAULTS, _JOINT_DEFAULTS, _SITE_DEFAULTS, XBody, XGeom,
                             XJoint, XModel, XSite, parse_mjcf_string, quat_normalize)
-from .compiler.model import ActuatorSpec, EntitySpec, Model, compile_scene
+from .compiler.model import (SENSOR_NAME_ATTRS, ActuatorSpec, EntitySpec, Model,
+                             compile_scene)
 
 
 class mjtJoint:  # noqa: N801 - MuJoCo's enum names
@@ -400,7 +401,7 @@ class Spec:
       host.sites += src.world.sites
     self._xml.excludes += [(prefix + a, prefix + b) for a, b in src.excludes]
     for tag, attrs in src.sensors:
-      self._xml.sensors.append((tag, {k: (prefix + v if k in ("site", "body", "joint", "objname", "name")
+      self._xml.sensors.append((tag, {k: (prefix + v if k in SENSOR_NAME_ATTRS + ("name",) and v != "world"
                                           else v) for k, v in attrs.items()}))
     for a in child.actuators:
       b = copy.deepcopy(a)
