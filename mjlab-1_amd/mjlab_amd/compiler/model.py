@@ -766,7 +766,7 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
     pairs.append((i, j) if gtype[i] <= gtype[j] else (j, i))
   # static terrain pairs last, grouped by their static geom (a heightfield, or a box welded
   # to the world): the engine's terrain broadphase walks them as per-geom blocks behind
-  # chunk / geom bounding-box culls; capi.cpp checks the layout
+  # chunk / geom bounding-box culls; csrc/model_tables.h checks the layout
   static = (gtype == hfT) | ((gtype == GEOM_TYPES["box"]) & (wg == 0))
   def tail_key(pr):
     a, b = pr

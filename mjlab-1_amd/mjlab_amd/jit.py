@@ -41,7 +41,7 @@ ORDER = ["nq", "nv", "nu", "nbody", "njnt", "ngeom", "nsite", "nsensor", "nsenso
 
 
 def spec_dims(m) -> dict:
-  """The engine's Dims of a compiled model, as capi.cpp derives them at mjx_model_create (the
+  """The engine's Dims of a compiled model, as csrc/model_tables.h derives them at mjx_model_create (the
   terrain pair-tail tables included); nconmax / njmax are the caller's.  A mismatch with the
   engine's own derivation costs speed (find_spec falls back to the generic kernels), never
   correctness: the engine compares every field."""
@@ -52,7 +52,7 @@ def spec_dims(m) -> dict:
   np_all = int(m.npair)
   body = np.asarray(a["geom_bodyid"]).reshape(-1)
   weld = np.asarray(a["body_weldid"]).reshape(-1)
-  static = (gt == 1) | ((gt == 6) & (weld[body] == 0))  # capi.cpp is_static
+  static = (gt == 1) | ((gt == 6) & (weld[body] == 0))  # model_tables.h is_static
   nreg = 0
   while nreg < np_all and not static[p1[nreg]] and not static[p2[nreg]]:
     nreg += 1
