@@ -1287,6 +1287,19 @@ __device__ __forceinline__ void solref_kb(const float* sref, const float* simp, 
 // efc_cid row code: type (2 bits) | payload << 2; payload = contact index, or for joint
 // limits joint | dof << 8
 __device__ __forceinline__ int efc_code(int type, int payload) { return type | payload << 2; }
+// con_dim holds the contact's condim, or 0 for a contact in its gap (margin - gap <= dist <
+// margin; mjContact.exclude = 1): it stays in the contact list, has no rows and no force
+__device__ __forceinline__ int con_nrows(int cd) { return cd <= 1 ? cd : 2 * (cd - 1); }
+// contact c's force in its frame (normal, two tangents) from its rows' forces
+__device__ __forceinline__ V3 con_frame_force(const float* S, const int* Si, const Lds& L, int c) {
+  const int cd = Si[L.con_dim + c];
+  if (cd == 0) return V3{0, 0, 0};
+  const int r0 = Si[L.con_efc + c];
+  if (cd == 1) return V3{S[L.efc_force + r0], 0, 0};
+  const float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
+  const float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
+  return V3{e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
+}
 
 // --------------------------------------------------------------------------- specialisation
 // ModelSpec<SP>: SP > 0 is the SP-th entry of specs.inc (scripts/gen_specs.py); its dims
@@ -1880,14 +1893,7 @@ __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* 
     m2 = m.geom_csmask1[g2] & m.geom_csmask2[g1];
     if (all) {  // (before the last substep only found counts are computed: no forces)
       dist = S[L.con_dist + c];
-      const int r0 = Si[L.con_efc + c];
-      if (Si[L.con_dim + c] == 1) {
-        fc.x = S[L.efc_force + r0];
-      } else {
-        float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-        float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-        fc = {e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
-      }
+      fc = con_frame_force(S, Si, L, c);
       fg = frame_tv(S + L.con_n + 3 * c, fc);
     }
   }
@@ -2962,8 +2968,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         (void)f1;
         S[L.con_mu + 2 * c] = fmaxf(MINMU, f0);
         S[L.con_mu + 2 * c + 1] = fmaxf(MINMU, f0);
-        Si[L.con_dim + c] = dim;
-        const float imargin = fmaxf(gmar[g1], gmar[g2]) - fmaxf(ggap[g1], ggap[g2]);
+        const float cmargin = fmaxf(gmar[g1], gmar[g2]);
+        const float imargin = cmargin - fmaxf(ggap[g1], ggap[g2]);
+        // in its gap (margin - gap <= dist < margin): kept, without rows (con_nrows); the band is
+        // empty without a gap, where the contact the narrowphase admits at dist == margin keeps its rows
+        Si[L.con_dim + c] = (dist >= imargin && dist < cmargin) ? 0 : dim;
         S[L.con_imargin + c] = imargin;
         // row impedance and reference K, B are per contact: computed once here
         S[L.con_imp + c] = impedance(si, dist, imargin);
@@ -3073,24 +3082,21 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       int cdim = 0, crow = 0, con_total = 0, con_off = 0;
       if (con1) {
         cdim = lane < ncon ? Si[L.con_dim + lane] : 0;
-        crow = lane < ncon ? (cdim == 1 ? 1 : 2 * (cdim - 1)) : 0;
-        if (lane < ncon && cdim != 1 && cdim != 3) atomicOr(&ints[3], 4);
+        crow = lane < ncon ? con_nrows(cdim) : 0;
+        if (lane < ncon && cdim > 1 && cdim != 3) atomicOr(&ints[3], 4);
         con_off = wave_excl_scan(crow, lane, &con_total);
       } else {
         for (int c0 = 0; c0 < ncon; c0 += kWave) {
           const int c = c0 + lane;
           const int cd = c < ncon ? Si[L.con_dim + c] : 0;
-          const int cr = c < ncon ? (cd == 1 ? 1 : 2 * (cd - 1)) : 0;
-          if (c < ncon && cd != 1 && cd != 3) atomicOr(&ints[3], 4);
+          const int cr = c < ncon ? con_nrows(cd) : 0;
+          if (c < ncon && cd > 1 && cd != 3) atomicOr(&ints[3], 4);
           int tot, off = wave_excl_scan(cr, lane, &tot);
           if (c < ncon) Si[L.con_efc + c] = con_total + off;
           con_total += tot;
         }
       }
-      auto con_rows = [&](int c) {
-        const int cd = Si[L.con_dim + c];
-        return cd == 1 ? 1 : 2 * (cd - 1);
-      };
+      auto con_rows = [&](int c) { return con_nrows(Si[L.con_dim + c]); };
       int nefc = lim_total + con_total;
       if (P->ovf_resolve) {
         // contacts or rows past this carve: list the world for the re-solve at full capacity
@@ -3162,7 +3168,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         for (int c = lane; c < ncon; c += kWave) {
           const int cbk = Si[L.con_key + c];
           const uint64_t m1 = m.body_dofmask[cb_b1(cbk)], m2 = m.body_dofmask[cb_b2(cbk)];
-          xbranch |= (m1 & ~m2) != 0ull && (m2 & ~m1) != 0ull;
+          xbranch |= Si[L.con_dim + c] != 0 && (m1 & ~m2) != 0ull && (m2 & ~m1) != 0ull;
         }
       }
       const int dense_h = __ballot(xbranch) != 0ull || !kTree<SP>;
@@ -3198,7 +3204,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         float jn = dot(F.n, jd);
         if (dim == 1) {
           Jg[r0 * nvp + i] = jn;
-        } else {
+        } else if (dim != 0) {
           float jt1 = dot(F.t, jd);
           float jt2 = dot(F.b, jd);
           Jg[(r0 + 0) * nvp + i] = jn + mu0 * jt1;
@@ -3393,15 +3399,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          int r0 = Si[L.con_efc + c];
-          V3 f = {0, 0, 0};
-          if (Si[L.con_dim + c] == 1) {
-            f.x = S[L.efc_force + r0];
-          } else {
-            float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-            float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-            f = {e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
-          }
+          const V3 f = con_frame_force(S, Si, L, c);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -3427,15 +3425,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              int r0 = Si[L.con_efc + c];
-              if (Si[L.con_dim + c] == 1) { oo[0] = S[L.efc_force + r0]; oo[1] = oo[2] = 0; }
-              else {
-                float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-                float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-                oo[0] = e0 + e1 + e2 + e3;
-                oo[1] = (e0 - e1) * S[L.con_mu + 2 * c];
-                oo[2] = (e2 - e3) * S[L.con_mu + 2 * c + 1];
-              }
+              const V3 f = con_frame_force(S, Si, L, c);
+              oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
             }
           }
         }
@@ -4045,15 +4036,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          int r0 = Si[L.con_efc + c];
-          V3 f = {0, 0, 0};
-          if (Si[L.con_dim + c] == 1) {
-            f.x = S[L.efc_force + r0];
-          } else {
-            float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-            float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-            f = {e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
-          }
+          const V3 f = con_frame_force(S, Si, L, c);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -4079,15 +4062,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              int r0 = Si[L.con_efc + c];
-              if (Si[L.con_dim + c] == 1) { oo[0] = S[L.efc_force + r0]; oo[1] = oo[2] = 0; }
-              else {
-                float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-                float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-                oo[0] = e0 + e1 + e2 + e3;
-                oo[1] = (e0 - e1) * S[L.con_mu + 2 * c];
-                oo[2] = (e2 - e3) * S[L.con_mu + 2 * c + 1];
-              }
+              const V3 f = con_frame_force(S, Si, L, c);
+              oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
             }
           }
         }
@@ -4104,15 +4080,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       const int nout = min(P->con_stride, D.wstats[8 * (size_t)w + 6]);  // phase A's output slots
       for (int c = lane; c < nout; c += kWave) {
         V3 f = {0, 0, 0};
-        if (c < ncon && nefc > 0) {
-          int r0 = Si[L.con_efc + c];
-          if (Si[L.con_dim + c] == 1) f.x = S[L.efc_force + r0];
-          else {
-            float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
-            float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-            f = {e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
-          }
-        }
+        if (c < ncon && nefc > 0) f = con_frame_force(S, Si, L, c);
         D.contact_force[(wc + c) * 3] = f.x;
         D.contact_force[(wc + c) * 3 + 1] = f.y;
         D.contact_force[(wc + c) * 3 + 2] = f.z;

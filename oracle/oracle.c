@@ -1030,6 +1030,10 @@ static void make_constraint(const mjxModelDesc* m, orcData* d) {
   for (int c = 0; c < d->ncon; c++) {
     orcContact* con = d->contact + c;
     con->efc_address = -1;
+    /* in its gap, margin - gap <= dist < margin (mjContact.exclude = 1): the contact stays
+     * listed, without rows or force.  The band is empty without a gap. */
+    if (con->dist >= con->includemargin &&
+        con->dist < fmax(m->geom_margin[con->geom1], m->geom_margin[con->geom2])) continue;
     int b1 = m->geom_bodyid[con->geom1], b2 = m->geom_bodyid[con->geom2];
     jac_point(m, d, b1, con->pos, jp1, NULL);
     jac_point(m, d, b2, con->pos, jp2, NULL);

@@ -17,7 +17,14 @@ compiles them through `mjlab_amd.spec.Spec` as tests/invariants.py does:
     a fixed-base arm beside them; `fallbacks26` has the same joint and child counts in one tree;
   - `robot_object`: an articulated free tree followed by a single free body, the last id;
   - `rows64`: a many-legged free tree whose seeded worlds make at most 64 and more than 64
-    constraint rows (the engine's lane-per-row boundary), below the 160-row fast carve.
+    constraint rows (the engine's lane-per-row boundary), below the 160-row fast carve;
+  - `params14`, `params38`: free trees (padded to 16 dofs: the lane-group form of the Jacobian
+    loop; to 40: one lane per dof) whose geoms, floor and limited joints carry non-default
+    constraint parameters in the MJCF: priority 0 / 1, condim 1 / 3, own friction, solmix,
+    solref (some in the direct negative form), solimp, margin and gap; limit margins, solreflimit
+    and solimplimit, and some ranges narrower than twice the margin.  Their states put a contact
+    in its gap (margin - gap <= dist < margin) and both sides of a limit at once in at least a
+    quarter of the worlds each, every activation test TIE_CLEARANCE from equality.
 
 Every model has skewed joint axes, geoms offset from the body origin (offset inertias),
 non-identity body quaternions, some armature, damping and stiffness (with a springref away
@@ -79,6 +86,8 @@ def _unit(v):
 
 class Builder:
   """Seeded generator of bodies, joints and geoms; collects actuated joints and sensors."""
+
+  floor_attrs = ""  # further XML attributes of the plane
 
   def __init__(self, seed: int, collide: bool = True):
     self.rng = np.random.default_rng(seed)
@@ -187,7 +196,7 @@ class Builder:
 
   def xml(self) -> str:
     lines = ['<mujoco>', '  <compiler angle="radian"/>', '  <option timestep="0.004"/>', '  <worldbody>',
-             '    <geom name="floor" type="plane" size="5 5 0.1" contype="1" conaffinity="0"/>']
+             f'    <geom name="floor" type="plane" size="5 5 0.1" contype="1" conaffinity="0"{self.floor_attrs}/>']
     for r in self.roots:
       lines += self._body_xml(r, "    ")
     lines += ['  </worldbody>', '  <sensor>'] + ["    " + s for s in self.sensors] + ['  </sensor>', '</mujoco>']
@@ -201,6 +210,56 @@ class Builder:
                                damping=float(self.rng.uniform(0.3, 1.5)), effort_limit=40.0,
                                armature=float(spec.joint(j).armature))
     return spec.compile()
+
+
+class ParamBuilder(Builder):
+  """A Builder whose geoms, floor and limited joints have non-default constraint parameters."""
+
+  floor_attrs = (' priority="0" condim="3" friction="0.8 0.005 0.0001" solmix="0.6" solref="0.015 0.9"'
+                 ' solimp="0.85 0.97 0.004 0.4 3" margin="0.006" gap="0.003"')
+
+  def __init__(self, seed: int):
+    super().__init__(seed)
+    self.ngeom = 0
+
+  def _solimp(self):
+    rng = self.rng
+    dmin = rng.uniform(0.6, 0.9)
+    return _fmt([dmin, rng.uniform(dmin, 0.98), rng.uniform(0.002, 0.02), rng.uniform(0.3, 0.7),
+                 float(rng.integers(1, 4))])
+
+  def geom(self, kind=None, collide=None, reach=0.08):
+    g = super().geom(kind, collide, reach)
+    rng, k = self.rng, self.ngeom
+    self.ngeom += 1
+    margin = rng.uniform(0.004, 0.02)
+    solref = [-rng.uniform(500.0, 2000.0), -rng.uniform(20.0, 60.0)] if k % 4 == 1 else \
+      [rng.uniform(0.012, 0.04), rng.uniform(0.7, 1.3)]
+    g.update(priority=str(k % 2), condim="3" if k % 3 else "1",
+             friction=_fmt([rng.uniform(0.4, 1.3), 0.005, 0.0001]), solmix=f"{rng.uniform(0.3, 2.0):.4g}",
+             solref=_fmt(solref), solimp=self._solimp(), margin=f"{margin:.4g}",
+             gap=f"{margin * rng.uniform(0.3, 0.7):.4g}")
+    return g
+
+  def joint(self, type="hinge"):
+    j = super().joint(type)
+    if "limited" in j.attrs:
+      rng = self.rng
+      k = int(j.name[1:])
+      scale = 3.0 if type == "hinge" else 1.0  # radians, metres
+      margin = scale * rng.uniform(0.006, 0.02)
+      if k % 10 == 2:  # narrower than twice the margin: both limit rows can be active at once
+        half = 0.5 * margin * rng.uniform(0.8, 1.4)
+        j.attrs["range"] = f"{-half:.5g} {half:.5g}"
+      j.attrs.update(margin=f"{margin:.5g}", solreflimit=_fmt([rng.uniform(0.01, 0.04), rng.uniform(0.7, 1.3)]),
+                     solimplimit=self._solimp())
+    return j
+
+
+def _param_tree(nv, seed):
+  b = ParamBuilder(seed)
+  b.grow(b.free_root((0.0, 0.0, 0.6)), nv - 6)
+  return b
 
 
 # ----------------------------------------------------------------------------- the models
@@ -350,6 +409,9 @@ _RECIPES = {
   "free21": (lambda: _free_tree(21, 124), dict(nv=21)),
   "free32": (lambda: _free_tree(32, 125), dict(nv=32)),
   "free37": (lambda: _free_tree(37, 126), dict(nv=37)),
+  # non-default constraint parameters (contacts in their gap, two-sided limits)
+  "params14": (lambda: _param_tree(14, 127), dict(nv=14, params=True)),
+  "params38": (lambda: _param_tree(38, 128), dict(nv=38, params=True)),
 }
 NAMES = tuple(_RECIPES)
 # Models mjx_model_create refuses ("Model shapes pinned by test"), with the
@@ -379,6 +441,31 @@ def _quat_mul(a, b):
 def surface_heights(m, od, q):
   """[(root body, z)] of every point a colliding geom can touch the plane with at qpos `q`: a
   sphere's lowest point, both ends of a capsule (position stage of the fp64 oracle `od`)."""
+  return [(r, z) for r, _, z in surface_points(m, od, q)]
+
+
+def contact_thresholds(m, g):
+  """The distances at which geom `g` against the plane changes what the step computes: touching,
+  the contact's margin (it exists below it) and margin - gap (it has rows below it)."""
+  plane = int(np.flatnonzero(np.asarray(m.geom_type) == GEOM_PLANE)[0])
+  margin = max(float(m.arrays["geom_margin"][g]), float(m.arrays["geom_margin"][plane]))
+  gap = max(float(m.arrays["geom_gap"][g]), float(m.arrays["geom_gap"][plane]))
+  return 0.0, margin, margin - gap
+
+
+def limit_distances(m, q):
+  """[(joint, lower dist, upper dist, margin)] of the limited joints at qpos `q`."""
+  out = []
+  for j in range(m.njnt):
+    if int(m.jnt_limited[j]) and int(m.jnt_type[j]) in (JNT_SLIDE, JNT_HINGE):
+      x = float(q[int(m.jnt_qposadr[j])])
+      lo, hi = (float(v) for v in np.asarray(m.arrays["jnt_range"])[j])
+      out.append((j, x - lo, hi - x, float(m.arrays["jnt_margin"][j])))
+  return out
+
+
+def surface_points(m, od, q):
+  """[(root body, geom, z)]: surface_heights with the geom of each point."""
   od.qpos[:] = q
   od.qvel[:] = 0.0
   od.forward()
@@ -392,10 +479,10 @@ def surface_heights(m, od, q):
     z = od.geom_xpos[g, 2] - gsize[g, 0]
     if int(gtype[g]) == GEOM_CAPSULE:
       dz = od.geom_xmat[g].reshape(3, 3)[2, 2] * gsize[g, 1]
-      out += [(r, float(z - dz)), (r, float(z + dz))]
+      out += [(r, g, float(z - dz)), (r, g, float(z + dz))]
     else:
       assert int(gtype[g]) == GEOM_SPHERE, "zoo geoms are spheres and capsules"
-      out.append((r, float(z)))
+      out.append((r, g, float(z)))
   return out
 
 
@@ -446,6 +533,23 @@ class ZooModel:
         q[:, a] += rng.uniform(-0.06, 0.06, n) if self.props.get("rows64") else rng.uniform(-0.5, 0.5, n)
       else:
         q[:, a] += rng.uniform(-0.08, 0.08, n)
+    params = bool(self.props.get("params"))
+    if params:
+      # every limited joint clear of its activation distances; in every other world the joints
+      # whose range is narrower than twice their margin sit where both limit rows are active
+      for w in range(n):
+        for j, _, _, mg in limit_distances(m, q[w]):
+          a = int(m.jnt_qposadr[j])
+          lo, hi = (float(v) for v in np.asarray(m.arrays["jnt_range"])[j])
+          c = 2 * TIE_CLEARANCE
+          if w % 2 == 0 and hi - mg + c < lo + mg - c:
+            q[w, a] = rng.uniform(hi - mg + c, lo + mg - c)
+          else:  # inside, within a margin, or past a limit by at most half the margin
+            q[w, a] = rng.uniform(lo - 0.5 * mg, hi + 0.5 * mg)
+          for _ in range(100):
+            if all(abs(d - mg) > TIE_CLEARANCE for d in (q[w, a] - lo, hi - q[w, a])):
+              break
+            q[w, a] += 2.5 * TIE_CLEARANCE
     depth = rng.uniform(-0.008, 0.025, (n, max(len(free), 1)))
     if self.props.get("rows64"):
       depth = rng.uniform(0.0, 0.04, depth.shape)
@@ -454,10 +558,18 @@ class ZooModel:
       for k, (body, a) in enumerate(free):
         if body in low:
           q[w, a + 2] -= low[body] + depth[w, k]
+          if params and w % 4 == 1:  # the lowest surface point hovers in its contact's gap
+            _, g, z = min((p for p in surface_points(m, od, q[w]) if p[0] == body), key=lambda p: p[2])
+            _, mg, im = contact_thresholds(m, g)
+            q[w, a + 2] += rng.uniform(im + 3 * TIE_CLEARANCE, mg - 3 * TIE_CLEARANCE) - z
           # keep every surface point 2e-4 clear of touching exactly: the engine's fp32 and the
           # oracle's fp64 distance must fall on the same side of the activation distance
           for _ in range(100):
-            if all(abs(z) > TIE_CLEARANCE for r, z in surface_heights(m, od, q[w]) if r == body):
+            if params:  # clear of touching, of the margin and of margin - gap
+              if all(abs(z - t) > TIE_CLEARANCE for r, g, z in surface_points(m, od, q[w]) if r == body
+                     for t in contact_thresholds(m, g)):
+                break
+            elif all(abs(z) > TIE_CLEARANCE for r, z in surface_heights(m, od, q[w]) if r == body):
               break
             q[w, a + 2] -= 2.5 * TIE_CLEARANCE
     jq = np.array([m.jnt_qposadr[j] for j in m.actuator_trnid], dtype=int)

@@ -3,9 +3,10 @@
 Every zoo model the engine admits (zoo.RUNNABLE) runs on the generic kernels
 (`specialize="never"`): all ten register-row lengths of csrc/engine.hip, padding lanes at every
 dof count mod 4, 60 dofs on 60 bodies, a 24-level chain, bodies with two and three joints and
-with five, six, seven and sixteen children, slides and joint springs, and constraint rows on
-both sides of 64.  16 worlds per model (32 for rows64), one GPU child process for the whole
-module (tests/zoo_child.py); `fallbacks26` runs once more on its run-time specialised kernels,
+with five, six, seven and sixteen children, slides and joint springs, constraint rows on
+both sides of 64, and (`params14`, `params38`) non-default contact and limit parameters with
+contacts in their gap and both rows of a limit at once.  16 worlds per model (32 for rows64),
+one GPU child process for the whole module (tests/zoo_child.py); `fallbacks26` runs once more on its run-time specialised kernels,
 which __graft_entry__.build() compiled into the in-tree cache (no compile happens here).  The
 models of zoo.REJECTED (more than 60 dofs, a tree after a tree of several bodies) are refused
 by mjx_model_create and launch nothing: tests/test_model_zoo_cpu.py asserts the refusals.
@@ -73,6 +74,8 @@ linear dof):
   free21                   21  0..13   0.007  0.002  0.004  0.002  0.002  0.023  0.370  0.002  0.000
   free32                   32  0..11   0.006  0.002  0.004  0.002  0.002  0.010  0.377  0.002  0.002
   free37                   37  1..13   0.007  0.002  0.006  0.004  0.004  0.020  0.295  0.005  0.005
+  params14                 14  1..11   0.008  0.001  0.001  0.001  0.001  0.016  0.247  0.001  0.000
+  params38                 38  3..19   0.007  0.003  0.003  0.003  0.002  0.020  0.336  0.001  0.000
   fallbacks26 (specialised) 26  1..24   0.007  0.002  0.005  0.002  0.002  0.022  0.406  0.003  0.003
 (no world needed the fp32 model: the largest qacc error is 0.011 of the test_gpu_parity bound
 and 0.074 of the fp32 model's.)
