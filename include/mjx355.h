@@ -61,6 +61,9 @@ enum { MJX_OBJ_NONE = 0, MJX_OBJ_BODY = 1, MJX_OBJ_XBODY = 2, MJX_OBJ_JOINT = 3,
 enum { MJX_REDUCE_NONE = 0, MJX_REDUCE_MINDIST = 1, MJX_REDUCE_MAXFORCE = 2,
        MJX_REDUCE_NETFORCE = 3 };
 enum { MJX_INT_EULER = 0, MJX_INT_IMPLICITFAST = 1 };
+/* equality types (mjtEq numbering); only MJX_EQ_JOINT is computed */
+enum { MJX_EQ_CONNECT = 0, MJX_EQ_WELD = 1, MJX_EQ_JOINT = 2, MJX_EQ_TENDON = 3, MJX_EQ_FLEX = 4,
+       MJX_EQ_DISTANCE = 5 };
 
 /* Host-side compiled model (fp64 / int32).  Field names follow mjModel.  Array
  * widths per element are in the trailing comment.  Filled by the Python scene
@@ -121,6 +124,21 @@ typedef struct mjxModelDesc_ {
    * entries of a real-valued sensor to [-cutoff, cutoff]; quaternion and axis sensors and
    * contact sensors are never clamped */
   const double* sensor_cutoff;
+  /* Equality constraints (appended).  Only joint equalities are computed (eq_type ==
+   * MJX_EQ_JOINT, mjEQ_JOINT): eq_obj1id / eq_obj2id are hinge or slide joints (eq_obj2id -1:
+   * none), eq_data[0..4] the polynomial coefficients; with d = qpos[j2] - qpos0[j2]
+   *   pos = qpos[j1] - qpos0[j1] - (c0 + c1 d + c2 d^2 + c3 d^3 + c4 d^4),
+   *   J[dof1] = 1, J[dof2] = -(c1 + 2 c2 d + 3 c3 d^2 + 4 c4 d^3), margin 0,
+   * impedance and reference acceleration from eq_solref / eq_solimp by the rules of limits and
+   * contacts.  The engine emits every equality with eq_active0 != 0 as two opposed one-sided
+   * rows (+J, +pos) and (-J, -pos) ahead of the limit and contact rows: nefc, njmax and every
+   * row counter (mjx_sim_stats) count TWO rows per active equality.  At most 64 equalities;
+   * mjx_model_create refuses any other eq_type, ids out of range, ball or free joints and
+   * obj1 == obj2; mjx_sim_create a row capacity below 2 neq.  Such a model runs the generic
+   * kernels.  A host that leaves neq 0 leaves the pointers unread. */
+  int neq;
+  const int32_t *eq_type, *eq_obj1id, *eq_obj2id, *eq_active0;
+  const double *eq_data /*5*/, *eq_solref /*2*/, *eq_solimp /*5*/;
 } mjxModelDesc;
 
 size_t mjx_model_desc_size(void); /* sizeof(mjxModelDesc): ABI check for FFI bindings */

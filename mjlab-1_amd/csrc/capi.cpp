@@ -92,14 +92,16 @@ struct Capacity {
 };
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
-static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid,
+static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid, int neq,
                          const char* too_big, Capacity& c) {
   c.d = d;
   for (int i = 0; i < 3; i++) {
     c.lds[i] = mjx::make_lds(d, i);
     if ((size_t)c.lds[i].total * 4 > 160 * 1024) return fail(too_big);
   }
-  c.spec = mjx::find_spec(d, dof_parentid.data());
+  // a model with joint equalities runs the generic kernels: no specialisation holds the
+  // equality rows' code (engine_impl.h neq_of)
+  c.spec = neq > 0 ? 0 : mjx::find_spec(d, dof_parentid.data());
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -277,7 +279,8 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
   mjx::DModel& dm = m->dm;
   // the descriptor's arrays (fields.h counts them over `d`; the pair lists are uploaded whole,
   // regular and terrain pairs)
-  mjx::Dims d = t.d;
+  // `d` as fields.h counts over it: the dims and the number of equalities (DModel::neq)
+  struct FieldDims : mjx::Dims { int neq; } d{t.d, t.neq};
   d.npair = t.d.npair_all;
 #define X_INT(name, cnt, w)                                                              \
   {                                                                                      \
@@ -302,6 +305,7 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
     return -1;
   // the derived tables
   dm.nmaskword = t.nmaskword;
+  dm.neq = t.neq;
   dm.ncsens = t.ncsens;
   const size_t nmask = (size_t)desc->nmaskword * d.nsensor;
   if (upload(m.get(), t.dof_ancmask, dm.dof_ancmask) || upload(m.get(), t.body_submask, dm.body_submask) ||
@@ -343,6 +347,8 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   if (nconmax <= 0 || nconmax > mjx::kWave)
     return fail("nconmax (contacts held per world) must be in [1, 64]");
   if (njmax <= 0) return fail("njmax must be positive");
+  if (njmax < 2 * model->t.neq)
+    return fail("njmax below the model's equality rows (two per equality constraint)");
   if (nconmax_max < nconmax || nconmax_max > mjx::kMaxContacts || njmax_max < njmax)
     return fail("max capacity: nconmax <= nconmax_max <= 512 and njmax <= njmax_max");
   if (nconmax_max > mjx::kWave && nconmax_max > njmax_max)
@@ -357,7 +363,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   mjx::Dims dims = model->t.d;
   dims.nconmax = nconmax;
   dims.njmax = njmax;
-  if (make_capacity(dims, model->t.dof_parentid,
+  if (make_capacity(dims, model->t.dof_parentid, model->t.neq,
                     "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
   s->nrowclass = mjx::choose_row_classes(s->fast.d, s->fast.spec, s->row_cap);
@@ -378,7 +384,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   if (s->has_big) {
     dims.nconmax = nconmax_max;
     dims.njmax = njmax_max;
-    if (make_capacity(dims, model->t.dof_parentid,
+    if (make_capacity(dims, model->t.dof_parentid, model->t.neq,
                       "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed

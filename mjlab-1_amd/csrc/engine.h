@@ -4,6 +4,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "fields.h"
@@ -25,7 +26,8 @@ constexpr int kSplitMinWorlds = 2048;  // batches at least this large run split
 constexpr int kMaxAirSlots = 8;  // contact-sensor slots with air-time tracking
 constexpr int kStaticChunk = 64; // terrain geoms per broadphase chunk
 
-enum { EFC_LIMIT = 0, EFC_FRICTIONLESS = 1, EFC_PYRAMIDAL = 2 };
+enum { EFC_LIMIT = 0, EFC_FRICTIONLESS = 1, EFC_PYRAMIDAL = 2, EFC_EQUALITY = 3 };
+constexpr int kMaxEq = 64;       // equalities per world: one lane each in phase A's row count
 enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_BOX = 6 };
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
 enum { SENS_GYRO = 0, SENS_VELOCIMETER = 1, SENS_ACCELEROMETER = 2, SENS_SUBTREEANGMOM = 3,
@@ -64,10 +66,8 @@ struct Opt {
 struct DModel {
 #define X_INT(name, cnt, w) const int32_t* name;
 #define X_FLT(name, cnt, w) const float* name; int name##_ws;
-  MJX_MODEL_INT_FIELDS(X_INT)
-  MJX_MODEL_FLOAT_FIELDS(X_FLT)
-#undef X_INT
-#undef X_FLT
+  MJX_MODEL_CORE_INT_FIELDS(X_INT)
+  MJX_MODEL_CORE_FLOAT_FIELDS(X_FLT)
   const uint64_t* dof_bodymask;
   const uint64_t* dof_ancmask;  // bit j set: dof j is dof i itself or an ancestor (host-derived)
   const uint64_t* body_submask;  // bit c set: body c is in body b's subtree (b included)
@@ -107,7 +107,22 @@ struct DModel {
   const int32_t* cs_sensor;
   const uint64_t* geom_csmask1;
   const uint64_t* geom_csmask2;
+  // Joint equalities (two constraint rows each): the eq_* fields of fields.h and their count.
+  // The count is not in Dims: no specs.inc entry or run-time specialisation has equalities, so
+  // their kernels take it as the constant 0 (engine_impl.h neq_of) and hold none of the equality
+  // code; a model with equalities runs the generic kernels (capi.cpp make_capacity).  The block
+  // is the struct's last 128 bytes: every other member of DModel keeps its offset and the
+  // members of Params behind the model keep theirs modulo 128, so the specialised kernels'
+  // scalar loads merge and schedule as they did without the block
+  // (profiles/equality_kernel_resources.txt).
+  MJX_MODEL_EQ_INT_FIELDS(X_INT)
+  MJX_MODEL_EQ_FLOAT_FIELDS(X_FLT)
+#undef X_INT
+#undef X_FLT
+  int neq;
+  int eq_reserved[12];
 };
+static_assert(sizeof(DModel) - offsetof(DModel, eq_type) == 128, "DModel: the equality block is 128 bytes");
 
 struct DData {
 #define X_FLT(name, cnt, w) float* name;

@@ -1285,8 +1285,32 @@ __device__ __forceinline__ void solref_kb(const float* sref, const float* simp, 
   }
 }
 // efc_cid row code: type (2 bits) | payload << 2; payload = contact index, or for joint
-// limits joint | dof << 8
+// limits joint | dof << 8, or for the two rows of an equality the equality's index
 __device__ __forceinline__ int efc_code(int type, int payload) { return type | payload << 2; }
+// Joint equality e (mjEQ_JOINT) at the world's qpos: with d = qpos[j2] - qpos0[j2] and poly the
+// quartic of eq_data, pos = qpos[j1] - qpos0[j1] - poly(d), J[dof1] = 1, J[dof2] = -poly'(d);
+// without a second joint (eq_obj2id < 0) pos = qpos[j1] - qpos0[j1] - c0 and dof2 = -1.
+struct EqRow { int dof1, dof2; float pos, j2; };
+__device__ __forceinline__ EqRow eq_row(const DModel& m, const float* eq_data, const float* qpos0,
+                                        const float* qpos, int e) {
+  const int j1 = m.eq_obj1id[e], j2 = m.eq_obj2id[e];
+  const float* c = eq_data + 5 * e;
+  const int a1 = m.jnt_qposadr[j1];
+  EqRow r;
+  r.dof1 = m.jnt_dofadr[j1];
+  r.dof2 = -1;
+  r.j2 = 0.f;
+  float poly = c[0];
+  if (j2 >= 0) {
+    const int a2 = m.jnt_qposadr[j2];
+    const float dq = qpos[a2] - qpos0[a2];
+    poly = c[0] + dq * (c[1] + dq * (c[2] + dq * (c[3] + dq * c[4])));
+    r.j2 = -(c[1] + dq * (2.f * c[2] + dq * (3.f * c[3] + dq * 4.f * c[4])));
+    r.dof2 = m.jnt_dofadr[j2];
+  }
+  r.pos = qpos[a1] - qpos0[a1] - poly;
+  return r;
+}
 // con_dim holds the contact's condim, or 0 for a contact in its gap (margin - gap <= dist <
 // margin; mjContact.exclude = 1): it stays in the contact list, has no rows and no force
 __device__ __forceinline__ int con_nrows(int cd) { return cd <= 1 ? cd : 2 * (cd - 1); }
@@ -1343,6 +1367,13 @@ template <int SP>
 __device__ __forceinline__ decltype(auto) dims_of(const Params* P) {
   if constexpr (SP > 0) return ModelSpec<SP>::dims();
   else return static_cast<const Dims&>(P->d);
+}
+// Joint equalities of the model: none in any specialisation (a constant, so the equality code
+// of phase A folds away there); the generic kernels read the count.
+template <int SP>
+__device__ __forceinline__ int neq_of(const Params* P) {
+  if constexpr (SP > 0) return 0;
+  else return P->m.neq;
 }
 template <int SP, int K>
 __device__ __forceinline__ decltype(auto) lds_of(const Params* P) {
@@ -3075,6 +3106,23 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         nlim_rows = (lim_mask & 1) + ((lim_mask >> 1) & 1);
       }
       int lim_total, lim_off = wave_excl_scan(nlim_rows, lane, &lim_total);
+      // Joint equalities (lane per equality) come first: rows are equality | limit | contact.
+      // An active equality makes two opposed one-sided rows (+J, +pos) and (-J, -pos) of the
+      // same D: their jar are opposite, so at most one is active at any x, and their summed
+      // cost, gradient and Hessian are those of one always-active row -- the Newton solver
+      // keeps its jar < 0 tests.  From here on lim_total / lim_off count from row 0: they
+      // include the equality rows (which are never dropped), and every contact offset below
+      // shifts with them.
+      const int neq = neq_of<SP>(P);
+      const float* eqdata = MF(eq_data);
+      int eq_total = 0, eq_off = 0;
+      bool eq_on = false;
+      if (neq > 0) {
+        eq_on = lane < neq && m.eq_active0[lane] != 0;
+        eq_off = wave_excl_scan(eq_on ? 2 : 0, lane, &eq_total);
+        lim_off += eq_total;
+        lim_total += eq_total;
+      }
       // contact rows: one contact per lane (offsets by one wave scan), or -- past 64 contacts
       // -- rounds of contacts lane + 64 r with a running carry, each contact's offset within
       // the contact rows kept in con_efc (made absolute below)
@@ -3160,6 +3208,16 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           r++;
         }
       }
+      // equality rows metadata -- lane per equality: the pair's signs and signed pos
+      if (neq > 0 && eq_on && nefc > 0) {
+        const float pos = eq_row(m, eqdata, qpos0, S + L.qpos, lane).pos;
+        for (int k = 0; k < 2; k++) {
+          const float sgn = k ? -1.f : 1.f;
+          Si[L.efc_cid + eq_off + k] = efc_code(EFC_EQUALITY, lane);
+          S[L.efc_aref + eq_off + k] = sgn * pos;  // temporarily: pos
+          S[L.efc_D + eq_off + k] = sgn;           // temporarily: jacobian sign
+        }
+      }
       // ints[6]: some contact couples two branches of the dof tree (neither body's dofs
       // contain the other's), so its rows fill the Newton Hessian outside the tree pattern
       // and phase B factors it densely; otherwise the tree form (rows_chol_tree)
@@ -3213,6 +3271,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           Jg[(r0 + 3) * nvp + i] = jn - mu1 * jt2;
         }
       };
+      // element i of equality row r (payload e): two dof entries, not the limit's one
+      auto eq_jelem = [&](int r, int e, int i) {
+        const EqRow q = eq_row(m, eqdata, qpos0, S + L.qpos, e);
+        const float sgn = S[L.efc_D + r];
+        return i == q.dof1 ? sgn : i == q.dof2 ? sgn * q.j2 : 0.f;
+      };
       if (con1 && ngrp == 1 && nvp <= kWave) {
         // One lane per dof and the contacts taken in turn by every lane: lane c forms contact
         // c's values once (frame, position, friction, first row, bodies, root coms) and keeps
@@ -3238,6 +3302,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         if (i < nvp) {
           for (int r = 0; r < lim_total && r < nefc; r++) {
             const int jd = Si[L.efc_cid + r] >> 2;
+            if (neq > 0 && r < eq_total) { Jg[r * nvp + i] = eq_jelem(r, jd, i); continue; }
             Jg[r * nvp + i] = (jd >> 8) == i ? S[L.efc_D + r] : 0.f;
           }
           if (i >= nv) {  // zero padding columns of the contact rows
@@ -3263,6 +3328,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         // limits
         for (int r = grp; r < lim_total && r < nefc; r += ngrp) {
           const int jd = Si[L.efc_cid + r] >> 2;
+          if (neq > 0 && r < eq_total) { Jg[r * nvp + i] = eq_jelem(r, jd, i); continue; }
           Jg[r * nvp + i] = (jd >> 8) == i ? S[L.efc_D + r] : 0.f;
         }
         if (i >= nv) {  // zero padding columns of the contact rows
@@ -3286,7 +3352,16 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const int code = Si[L.efc_cid + r];
         const int type = code & 3, pl = code >> 2;  // pl: contact, or joint | dof << 8
         float pos, margin, diag, imp, K, B;
-        if (type == EFC_LIMIT) {
+        EqRow eq = {0, -1, 0.f, 0.f};
+        if (neq > 0 && type == EFC_EQUALITY) {
+          const float* esolimp = MF(eq_solimp) + 5 * pl;
+          eq = eq_row(m, eqdata, qpos0, S + L.qpos, pl);
+          pos = S[L.efc_aref + r];
+          margin = 0.f;
+          diag = dinvw[eq.dof1] + (eq.dof2 >= 0 ? dinvw[eq.dof2] : 0.f);
+          imp = impedance(esolimp, pos, margin);
+          solref_kb(MF(eq_solref) + 2 * pl, esolimp, h, K, B);
+        } else if (type == EFC_LIMIT) {
           const int j = pl & 255;
           pos = S[L.efc_aref + r];
           margin = jmargin[j];
@@ -3312,7 +3387,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         float Rr = fmaxf(MINVAL, (1 - imp) * diag / imp);
         // efc_vel = J qvel, evaluated from the body velocities (cvel is the same chain sum)
         float vel;
-        if (type == EFC_LIMIT) {
+        if (neq > 0 && type == EFC_EQUALITY) {
+          vel = S[L.efc_D + r] *
+                (S[L.qvel + eq.dof1] + (eq.dof2 >= 0 ? eq.j2 * S[L.qvel + eq.dof2] : 0.f));
+        } else if (type == EFC_LIMIT) {
           vel = S[L.efc_D + r] * S[L.qvel + (pl >> 8)];
         } else {
           const int c = pl;
@@ -3331,7 +3409,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         S[L.efc_D + r] = 1.0f / Rr;
         S[L.efc_aref + r] = -B * vel - K * imp * (pos - margin);
       }
-      if (lane == 0) { ints[1] = nefc; ints[2] = lim_total; ints[4] = ncon; ints[6] = dense_h; }
+      if (lane == 0) { ints[1] = nefc; ints[2] = lim_total - eq_total; ints[4] = ncon; ints[6] = dense_h; }
       sync();
     }
     const int nefc = ints[1];

@@ -1,14 +1,14 @@
 // fields.h — single source of truth for the device model/data field tables.
 //
 // X(name, count, width): `count` is an expression over the model dims struct `d`
-// (mjxDims) and `width` the per-element width.  The same lists generate the device
-// structs (engine.hip), the upload code and the DLPack field table (capi.cpp), so the
-// Python-visible names match mjModel / mjData (sim/sim_data.py:177-240 exposes the
-// same names from MuJoCo-Warp).
+// (mjxDims, plus `neq`, the model's equality count: engine.h DModel::neq) and `width` the
+// per-element width.  The same lists generate the device structs (engine.hip), the upload
+// code and the DLPack field table (capi.cpp), so the Python-visible names match mjModel /
+// mjData (sim/sim_data.py:177-240 exposes the same names from MuJoCo-Warp).
 #pragma once
 
 // Model integer fields (never expanded per world).
-#define MJX_MODEL_INT_FIELDS(X)                                                        \
+#define MJX_MODEL_CORE_INT_FIELDS(X)                                                     \
   X(body_parentid, d.nbody, 1) X(body_rootid, d.nbody, 1) X(body_weldid, d.nbody, 1) \
   X(body_jntnum, d.nbody, 1) X(body_jntadr, d.nbody, 1) X(body_dofnum, d.nbody, 1)   \
   X(body_dofadr, d.nbody, 1) X(body_level, d.nbody, 1)                               \
@@ -27,10 +27,15 @@
   X(sensor_refid, d.nsensor, 1) X(sensor_adr, d.nsensor, 1) X(sensor_dim, d.nsensor, 1) \
   X(sensor_intprm, d.nsensor, 3) X(pair_geom1, d.npair, 1) X(pair_geom2, d.npair, 1) \
   X(hfield_nrow, d.nhfield, 1) X(hfield_ncol, d.nhfield, 1) X(hfield_adr, d.nhfield, 1)
+// ... of the joint equalities.  The device struct keeps the equality fields in a block of their
+// own behind everything else (engine.h DModel): only the generic kernels read them.
+#define MJX_MODEL_EQ_INT_FIELDS(X) \
+  X(eq_type, d.neq, 1) X(eq_obj1id, d.neq, 1) X(eq_obj2id, d.neq, 1) X(eq_active0, d.neq, 1)
+#define MJX_MODEL_INT_FIELDS(X) MJX_MODEL_CORE_INT_FIELDS(X) MJX_MODEL_EQ_INT_FIELDS(X)
 
 // Model float fields: uploaded as fp32, each may be expanded to one copy per world
 // (Simulation.expand_model_fields, sim/sim.py:226-240).
-#define MJX_MODEL_FLOAT_FIELDS(X)                                                      \
+#define MJX_MODEL_CORE_FLOAT_FIELDS(X)                                                 \
   X(body_pos, d.nbody, 3) X(body_quat, d.nbody, 4) X(body_ipos, d.nbody, 3)          \
   X(body_iquat, d.nbody, 4) X(body_mass, d.nbody, 1) X(body_inertia, d.nbody, 3)     \
   X(body_subtreemass, d.nbody, 1) X(body_invweight0, d.nbody, 2)                     \
@@ -47,6 +52,9 @@
   X(actuator_forcerange, d.nu, 2) X(actuator_ctrlrange, d.nu, 2)                     \
   X(hfield_size, d.nhfield, 4) X(hfield_data, d.nhfielddata, 1)                      \
   X(sensor_cutoff, d.nsensor, 1)
+#define MJX_MODEL_EQ_FLOAT_FIELDS(X) \
+  X(eq_data, d.neq, 5) X(eq_solref, d.neq, 2) X(eq_solimp, d.neq, 5)
+#define MJX_MODEL_FLOAT_FIELDS(X) MJX_MODEL_CORE_FLOAT_FIELDS(X) MJX_MODEL_EQ_FLOAT_FIELDS(X)
 
 // Per-world data fields, fp32, layout [nworld][count*width] (torch row-major).
 #define MJX_DATA_FLOAT_FIELDS(X)                                                       \

@@ -22,6 +22,7 @@ struct ModelTables {
   Dims d{};  // nconmax = njmax = 0: the sim sets its capacities
   Opt o{};
   int nmaskword = 0;
+  int neq = 0;     // joint equalities (fields.h counts the eq_* fields by it)
   int ncsens = 0;  // 0 past 64 single-slot contact sensors (phase C then matches serially)
   std::vector<int32_t> dof_parentid;  // as given: find_spec checks a specialisation's dof tree
   // engine.h DModel, the host-derived part
@@ -148,6 +149,28 @@ inline std::string build_sensor_ext(const mjxModelDesc& desc, std::vector<Sensor
   return "";
 }
 
+// Joint equalities: the only kind the engine computes, every id checked here (phase A indexes
+// jnt_* and qpos by them).
+inline std::string check_equalities(const mjxModelDesc& desc) {
+  if (desc.neq < 0) return "neq must not be negative";
+  if (desc.neq > kMaxEq) return "at most 64 equality constraints per world supported";
+  if (desc.neq > 0 && (!desc.eq_type || !desc.eq_obj1id || !desc.eq_obj2id || !desc.eq_active0 ||
+                       !desc.eq_data || !desc.eq_solref || !desc.eq_solimp))
+    return "neq > 0 with a null eq_* array";
+  for (int e = 0; e < desc.neq; e++) {
+    const std::string who = "equality " + std::to_string(e) + ": ";
+    if (desc.eq_type[e] != MJX_EQ_JOINT)
+      return who + "only joint equalities are supported (eq_type " + std::to_string(desc.eq_type[e]) + ")";
+    const int j1 = desc.eq_obj1id[e], j2 = desc.eq_obj2id[e];
+    if (j1 < 0 || j1 >= desc.njnt || j2 < -1 || j2 >= desc.njnt) return who + "joint id out of range";
+    if (j1 == j2) return who + "joint1 and joint2 are the same joint";
+    for (int j : {j1, j2})
+      if (j >= 0 && desc.jnt_type[j] != JNT_HINGE && desc.jnt_type[j] != JNT_SLIDE)
+        return who + "a joint equality takes hinge or slide joints";
+  }
+  return "";
+}
+
 // Sizes and options as the kernels take them (npair .. nstpartner: terrain_tables).
 inline void dims_and_options(const mjxModelDesc& desc, ModelTables& t) {
   Dims& d = t.d;
@@ -161,6 +184,7 @@ inline void dims_and_options(const mjxModelDesc& desc, ModelTables& t) {
   for (int b = 0; b < d.nbody; b++)
     if (desc.body_mocapid[b] >= 0) d.nmocap++;
   d.nconmax = 0; d.njmax = 0;
+  t.neq = desc.neq;
   Opt& o = t.o;
   o.timestep = (float)desc.timestep; o.tolerance = (float)desc.tolerance;
   o.ls_tolerance = (float)desc.ls_tolerance; o.impratio = (float)desc.impratio;
@@ -393,6 +417,7 @@ inline void contact_sensor_masks(const mjxModelDesc& desc, ModelTables& t) {
 // Fills `t` (a fresh ModelTables) from the descriptor.  Returns "" or the refusal.
 inline std::string build_model_tables(const mjxModelDesc& desc, ModelTables& t) {
   std::string err = tables::check_limits(desc);
+  if (err.empty()) err = tables::check_equalities(desc);
   if (err.empty()) err = tables::build_sensor_ext(desc, t.sensor_ext);
   if (err.empty() && desc.nmaskword < (desc.ngeom + 31) / 32) err = "nmaskword < ceil(ngeom / 32)";
   if (!err.empty()) return err;

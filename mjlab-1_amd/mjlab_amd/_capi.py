@@ -53,12 +53,16 @@ _ARRAYS = (
   + [("hfield_size", _D), ("hfield_data", _D)]
   + [("sensor_cutoff", _D)]
 )
+# appended after the arrays above: the equality count, then the eq_* arrays
+_EQ_ARRAYS = ([(n, _I) for n in ("eq_type", "eq_obj1id", "eq_obj2id", "eq_active0")]
+              + [(n, _D) for n in ("eq_data", "eq_solref", "eq_solimp")])
 
 
 class ModelDesc(ctypes.Structure):
   _fields_ = ([("abi_version", ctypes.c_int)] + [(n, ctypes.c_int) for n in _INT_SCALARS]
               + [(n, ctypes.c_double) for n in _REAL_SCALARS]
-              + [("gravity", ctypes.c_double * 3)] + list(_ARRAYS))
+              + [("gravity", ctypes.c_double * 3)] + list(_ARRAYS)
+              + [("neq", ctypes.c_int)] + list(_EQ_ARRAYS))
 
 
 _DTYPES = {_I: np.int32, _D: np.float64, _U64: np.uint64, _U32: np.uint32}
@@ -89,8 +93,15 @@ def make_desc(model) -> tuple[ModelDesc, list]:
   for i in range(3):
     d.gravity[i] = float(model.gravity[i])
   keep = []
-  for name, ct in _ARRAYS:
-    src = model.arrays[name] if name != "sensor_cutoff" else sensor_cutoff(model)
+  # (a model compiled without equalities carries no eq_* array: neq 0, the arrays unread)
+  d.neq = int(len(model.arrays.get("eq_type", ())))
+  for name, ct in list(_ARRAYS) + _EQ_ARRAYS:
+    if name == "sensor_cutoff":
+      src = sensor_cutoff(model)
+    elif (name, ct) in _EQ_ARRAYS:
+      src = model.arrays.get(name, ())
+    else:
+      src = model.arrays[name]
     arr = np.ascontiguousarray(np.asarray(src).reshape(-1), dtype=_DTYPES[ct])
     if arr.size == 0:
       arr = np.zeros(1, dtype=_DTYPES[ct])

@@ -5,7 +5,8 @@ This is the setup path that the reference delegates to MuJoCo's `MjSpec.from_fil
 `src/mjlab/scene/scene.py:38-48`).  Only the subset the mjlab robots use is
 supported: nested `<default>` classes and `childclass`, bodies with
 `<inertial>`, free/hinge/slide/ball joints, primitive geoms (plane, sphere,
-capsule, box, hfield placeholder) with `fromto`, sites, `<contact><exclude>` and
+capsule, box, hfield placeholder) with `fromto`, sites, `<contact><exclude>`, joint
+equalities (`<equality><joint>`; every other equality kind is refused by name) and
 `<sensor>` elements, kept as (tag, attributes) for the scene compiler (`compiler/model.py`
 `push_builtin`: the site, joint, subtree, actuator and frame sensors with MuJoCo's `objtype` /
 `objname` / `reftype` / `refname` / `cutoff` attributes).
@@ -42,8 +43,12 @@ _JOINT_DEFAULTS = dict(
 )
 _SITE_DEFAULTS = dict(pos=(0.0, 0.0, 0.0), quat=(1.0, 0.0, 0.0, 0.0), type="sphere",
                       size=(0.005, 0.005, 0.005))
+# <equality><joint>: MuJoCo's defaults (polycoef "0 1 0 0 0": joint1 follows joint2)
+_EQUALITY_DEFAULTS = dict(joint1=None, joint2=None, polycoef=(0.0, 1.0, 0.0, 0.0, 0.0),
+                          solref=(0.02, 1.0), solimp=(0.9, 0.95, 0.001, 0.5, 2.0), active="true")
+EQUALITY_KINDS = ("connect", "weld", "joint", "tendon", "flex", "distance")  # mjtEq order
 
-_FLOAT_VEC = {"size", "friction", "solref", "solimp", "pos", "quat", "axis", "range",
+_FLOAT_VEC = {"size", "friction", "solref", "solimp", "pos", "quat", "axis", "range", "polycoef",
               "solreflimit", "solimplimit", "fromto", "rgba", "diaginertia", "fullinertia",
               "euler", "axisangle", "zaxis", "xyaxes"}
 _FLOAT = {"solmix", "margin", "gap", "density", "stiffness", "damping", "armature",
@@ -152,6 +157,14 @@ class XSite:
 
 
 @dataclass
+class XEquality:
+  """A joint equality: attrs joint1, joint2 (None: joint1 alone), polycoef (5), solref, solimp,
+  active ("true" / "false")."""
+  name: str
+  attrs: dict
+
+
+@dataclass
 class XBody:
   name: str
   pos: np.ndarray
@@ -174,6 +187,7 @@ class XModel:
   angle_deg: bool
   eulerseq: str
   inertiafromgeom: str = "auto"  # <compiler inertiafromgeom>: "auto" | "true" | "false"
+  equalities: list = field(default_factory=list)  # XEquality, in file order
 
 
 class _Defaults:
@@ -181,9 +195,10 @@ class _Defaults:
     self.classes: dict[str, dict[str, dict]] = {}
 
   def build(self, elem, parent_cls: dict[str, dict] | None, name: str):
-    cls = copy.deepcopy(parent_cls) if parent_cls else {"geom": {}, "joint": {}, "site": {}}
+    cls = copy.deepcopy(parent_cls) if parent_cls else {"geom": {}, "joint": {}, "site": {},
+                                                        "equality": {}}
     for child in elem:
-      if child.tag in ("geom", "joint", "site"):
+      if child.tag in ("geom", "joint", "site", "equality"):
         cls[child.tag].update({k: _parse_attr(k, v) for k, v in child.attrib.items()})
     self.classes[name] = cls
     for child in elem:
@@ -232,11 +247,12 @@ def parse_mjcf_string(text: str) -> XModel:
   if dflt is not None:
     defaults.build(dflt, None, dflt.attrib.get("class", "main"))
   if "main" not in defaults.classes:
-    defaults.classes["main"] = {"geom": {}, "joint": {}, "site": {}}
+    defaults.classes["main"] = {"geom": {}, "joint": {}, "site": {}, "equality": {}}
 
   def resolve(tag, elem, childclass):
     cls_name = elem.attrib.get("class", childclass)
-    base = {"geom": _GEOM_DEFAULTS, "joint": _JOINT_DEFAULTS, "site": _SITE_DEFAULTS}[tag]
+    base = {"geom": _GEOM_DEFAULTS, "joint": _JOINT_DEFAULTS, "site": _SITE_DEFAULTS,
+            "equality": _EQUALITY_DEFAULTS}[tag]
     attrs = dict(base)
     attrs.update(defaults.classes.get("main", {}).get(tag, {}))
     if cls_name:
@@ -286,8 +302,25 @@ def parse_mjcf_string(text: str) -> XModel:
   if sens is not None:
     for s in sens:
       sensors.append((s.tag, dict(s.attrib)))
+  equalities = []
+  for section in root.findall("equality"):
+    for e in section:
+      if e.tag != "joint":
+        raise NotImplementedError(
+          f"<equality><{e.tag}>: only joint equalities are supported (connect, weld, tendon, "
+          "flex and distance equalities are not computed)")
+      attrs = resolve("equality", e, None)
+      if not attrs.get("joint1"):
+        raise ValueError("<equality><joint>: joint1 is required")
+      # fewer than five coefficients: the rest keep MuJoCo's defaults
+      pc = tuple(attrs["polycoef"])
+      if len(pc) > 5:
+        raise ValueError(f"<equality><joint>: polycoef takes at most 5 values, got {len(pc)}")
+      attrs["polycoef"] = pc + _EQUALITY_DEFAULTS["polycoef"][len(pc):]
+      attrs.pop("name", None)
+      equalities.append(XEquality(e.attrib.get("name", ""), attrs))
   return XModel(root.attrib.get("model", ""), world, excludes, sensors, angle_deg, eulerseq,
-                inertiafromgeom)
+                inertiafromgeom, equalities)
 
 
 def geom_frame(attrs: dict, angle_deg: bool, eulerseq: str):
@@ -329,9 +362,12 @@ def xmodel_to_dict(xm: XModel) -> dict:
                 geoms=[dict(name=g.name, attrs=_attrs_out(g.attrs)) for g in b.geoms],
                 sites=[dict(name=s.name, attrs=_attrs_out(s.attrs)) for s in b.sites],
                 children=[body(c) for c in b.children])
-  return dict(name=xm.name, world=body(xm.world), excludes=[list(e) for e in xm.excludes],
-              sensors=[[t, dict(a)] for t, a in xm.sensors], angle_deg=xm.angle_deg,
-              eulerseq=xm.eulerseq, inertiafromgeom=xm.inertiafromgeom)
+  d = dict(name=xm.name, world=body(xm.world), excludes=[list(e) for e in xm.excludes],
+           sensors=[[t, dict(a)] for t, a in xm.sensors], angle_deg=xm.angle_deg,
+           eulerseq=xm.eulerseq, inertiafromgeom=xm.inertiafromgeom)
+  if xm.equalities:  # (a description without equalities keeps the form it had)
+    d["equalities"] = [dict(name=e.name, attrs=_attrs_out(e.attrs)) for e in xm.equalities]
+  return d
 
 
 def xmodel_from_dict(d: dict) -> XModel:
@@ -344,4 +380,5 @@ def xmodel_from_dict(d: dict) -> XModel:
                  children=[body(c) for c in b["children"]], mocap=bool(b["mocap"]))
   return XModel(d["name"], body(d["world"]), [tuple(e) for e in d["excludes"]],
                 [(t, dict(a)) for t, a in d["sensors"]], bool(d["angle_deg"]), d["eulerseq"],
-                d.get("inertiafromgeom", "auto"))
+                d.get("inertiafromgeom", "auto"),
+                [XEquality(e["name"], _attrs_in(e["attrs"])) for e in d.get("equalities", [])])

@@ -253,6 +253,11 @@ class Model:
   def name2id(self, kind: str, name: str) -> int:
     return self.names[kind].index(name)
 
+  @property
+  def neq(self) -> int:
+    """Equality constraints; a model without any carries no eq_* array."""
+    return int(len(self.__dict__.get("arrays", {}).get("eq_type", ())))
+
 
 def _resolve(value, names, default):
   """`resolve_field` of mjlab's spec_config (utils/string.py:5-38): scalar or
@@ -417,6 +422,7 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   B.add_body("world", -1, np.zeros(3), np.array([1.0, 0, 0, 0]), None)
   geoms, sites, joints = [], [], []
   excludes = []
+  equalities = []  # joint equalities of every entity, names prefixed
   xml_sensors = []
   keyframe_parts = []  # (qposadr, values)
   actuators = []
@@ -526,6 +532,12 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
       add_geom(0, prefix + g.name if g.name else "", dict(g.attrs), xml)
     for (b1, b2) in xml.excludes:
       excludes.append((prefix + b1, prefix + b2))
+    for e in getattr(xml, "equalities", ()):
+      a = e.attrs
+      equalities.append(dict(name=prefix + e.name if e.name else "", joint1=prefix + a["joint1"],
+                             joint2=prefix + a["joint2"] if a.get("joint2") else None,
+                             polycoef=a["polycoef"], solref=a["solref"], solimp=a["solimp"],
+                             active=str(a.get("active", "true")).lower() != "false"))
     for tag, attrs in xml.sensors:
       xml_sensors.append((tag, {k: (prefix + v if k in SENSOR_NAME_ATTRS and v != "world"
                                     else v) for k, v in attrs.items()},
@@ -601,6 +613,31 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   A["jnt_margin"] = np.array([j["attrs"]["margin"] for j in joints], float)
   A["jnt_stiffness"] = np.array([j["attrs"]["stiffness"] for j in joints], float)
   m.names["joint"] = [j["name"] for j in joints]
+  # joint equalities (mjEQ_JOINT = 2; eq_data holds polycoef).  A model without any carries no
+  # eq_* array and no names["equality"]: the shipped scenes compile to what they were.
+  if equalities:
+    jn = m.names["joint"]
+    obj = np.full((len(equalities), 2), -1, np.int32)
+    for k, e in enumerate(equalities):
+      who = f"equality '{e['name']}'" if e["name"] else f"equality {k}"
+      for c, key in enumerate(("joint1", "joint2")):
+        if e[key] is None:
+          continue
+        if e[key] not in jn:
+          raise ValueError(f"{who}: no joint '{e[key]}'")
+        obj[k, c] = jn.index(e[key])
+        if int(jtype[obj[k, c]]) not in (JOINT_TYPES["slide"], JOINT_TYPES["hinge"]):
+          raise ValueError(f"{who}: joint '{e[key]}' is not a hinge or slide joint "
+                           "(a joint equality couples scalar joints)")
+      if obj[k, 0] == obj[k, 1]:
+        raise ValueError(f"{who}: joint1 and joint2 are the same joint '{e['joint1']}'")
+    A["eq_type"] = np.full(len(equalities), 2, np.int32)
+    A["eq_obj1id"], A["eq_obj2id"] = obj[:, 0].copy(), obj[:, 1].copy()
+    A["eq_active0"] = np.array([1 if e["active"] else 0 for e in equalities], np.int32)
+    A["eq_data"] = np.array([e["polycoef"] for e in equalities], float).reshape(-1, 5)
+    A["eq_solref"] = np.array([e["solref"] for e in equalities], float).reshape(-1, 2)
+    A["eq_solimp"] = np.array([e["solimp"] for e in equalities], float).reshape(-1, 5)
+    m.names["equality"] = [e["name"] for e in equalities]
 
   body_jntadr = np.full(nbody, -1, np.int32)
   body_jntnum = np.zeros(nbody, np.int32)

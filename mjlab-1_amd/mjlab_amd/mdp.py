@@ -11,6 +11,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from .managers import (ActionTerm, ActionTermCfg, CommandTerm, CommandTermCfg, SceneEntityCfg,
@@ -475,7 +476,17 @@ FIELD_SPECS = {
   "geom_quat": ("geom", [0, 1, 2, 3], None), "geom_rgba": ("geom", [0, 1, 2, 3], None),
   "site_pos": ("site", [0, 1, 2], None), "site_quat": ("site", [0, 1, 2, 3], None),
   "qpos0": ("qpos", None, None),
+  # joint equalities (no reference counterpart): those whose first joint is the entity's
+  "eq_data": ("equality", [0, 1, 2, 3, 4], None), "eq_solref": ("equality", [0, 1], None),
+  "eq_solimp": ("equality", [0, 1, 2, 3, 4], None),
 }
+
+
+def _entity_equalities(env, ix) -> torch.Tensor:
+  """Ids of the model's equalities whose first joint belongs to the entity."""
+  obj1 = np.asarray(env.sim.mj_model.arrays.get("eq_obj1id", ()), np.int64)
+  own = np.isin(obj1, ix.joint_ids.cpu().numpy())
+  return torch.as_tensor(np.flatnonzero(own), dtype=torch.long, device=env.device)
 
 
 def _sample_distribution(distribution, lo, hi, shape, device):
@@ -509,7 +520,8 @@ def randomize_field(env, env_ids, field: str, ranges, distribution: str = "unifo
          "joint": lambda: ix.joint_ids[asset_cfg.joint_ids],
          "body": lambda: ix.body_ids[asset_cfg.body_ids],
          "geom": lambda: ix.geom_ids[asset_cfg.geom_ids],
-         "site": lambda: ix.site_ids[asset_cfg.site_ids]}[etype]()
+         "site": lambda: ix.site_ids[asset_cfg.site_ids],
+         "equality": lambda: _entity_equalities(env, ix)}[etype]()
   field_ndim = t.dim() - 1
   if axes is not None:
     target = list(axes)

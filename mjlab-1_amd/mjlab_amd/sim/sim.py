@@ -207,6 +207,11 @@ def _stream_handle(device: torch.device) -> int:
   return torch.cuda.current_stream(device).cuda_stream
 
 
+def _neq(model) -> int:
+  """Equality constraints of a compiled model (none: no eq_* array)."""
+  return int(len(model.arrays.get("eq_type", ())))
+
+
 def world_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
   """Per-world contact/row capacities of the fast LDS carve."""
   if os.environ.get("MJX355_WORLD_CAPACITY"):  # diagnostic: "ncon,rows"
@@ -221,7 +226,8 @@ def world_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
     ncon = cfg.nconmax if cfg.nconmax is not None else 48
     ncon, cap = int(min(64, max(ncon, 48))), 160
   rows = cfg.njmax if cfg.njmax is not None else cap
-  rows = int(max(1, min(rows, 4 * ncon + 2 * nlim, cap)))
+  # (two rows per joint equality: they come first and are never dropped)
+  rows = int(max(1, min(rows, 4 * ncon + 2 * nlim + 2 * _neq(model), cap)))
   return ncon, rows
 
 
@@ -242,7 +248,7 @@ def max_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
   if os.environ.get("MJX355_RESOLVE", "1") == "0" or os.environ.get("MJX355_WORLD_CAPACITY"):
     return ncon, rows
   nlim = int(np.sum(model.jnt_limited)) if model.njnt else 0
-  rmax = int(cfg.njmax) if cfg.njmax is not None else 4 * 64 + 2 * nlim
+  rmax = int(cfg.njmax) if cfg.njmax is not None else 4 * 64 + 2 * nlim + 2 * _neq(model)
   rmax = max(rows, rmax)
   cmax = min(rmax, MAX_CONTACTS)
   return max(ncon, cmax), rmax
@@ -284,7 +290,7 @@ def _warn_capacity(cfg: SimulationCfg, model, ncon: int, rows: int) -> None:
   # rows past 4 * ncon + 2 * (limited joints) cannot occur (every row belongs to a pyramidal
   # contact or a joint limit): warn only when the capacity is below what njmax allows of that
   nlim = int(np.sum(model.jnt_limited)) if model.njnt else 0
-  reachable = 4 * ncon + 2 * nlim
+  reachable = 4 * ncon + 2 * nlim + 2 * _neq(model)
   if (cfg.njmax is not None and min(cfg.njmax, reachable) > rows) and asked not in _capacity_warned:
     _capacity_warned.add(asked)
     import warnings
@@ -304,6 +310,10 @@ class Simulation:
     self.num_envs = int(num_envs)
     self.line_search = "exact"  # whatever cfg.ls_parallel says (see SimulationCfg.ls_parallel)
     self._default_model_fields: dict[str, torch.Tensor] = {}
+    if cfg.specialize == "always" and _neq(model) > 0:
+      raise NotImplementedError(
+          "specialize='always': a model with equality constraints runs the generic kernels only "
+          "(equalities are not compiled into specialised or JIT kernels)")
     dev = torch.device(device)
     if dev.type != "cuda":
       raise MjxError("mjlab_amd.Simulation runs only on a ROCm GPU (device 'cuda:N'); "
@@ -583,6 +593,11 @@ class Simulation:
     env = os.environ.get("MJX355_JIT")
     if env is not None:
       policy = "always" if env != "0" else "never"
+    if _neq(model) > 0:
+      # equality rows exist only in the generic kernels (csrc/engine_impl.h neq_of): a
+      # specialisation is neither looked up nor compiled, and jit.spec_dims never asked
+      # (specialize="always" was refused when the Simulation was created)
+      return False
     if policy == "never" or os.environ.get("MJX355_NO_SPEC"):
       return False
     from .. import jit

@@ -5,7 +5,7 @@ edits models programmatically the way the reference does with `mujoco.MjSpec`
 
 Only what the engine runs is modelled: a body tree with free / hinge / slide joints,
 primitive geoms, sites, mocap bodies, joint-transmission actuators with fixed gain and
-affine bias, keyframes, `attach` with a name prefix, and `compile()` to the flat `Model`
+affine bias, joint equalities (`add_equality`; every other kind raises), keyframes, `attach` with a name prefix, and `compile()` to the flat `Model`
 the engine and the oracle load.  Enum names follow MuJoCo's (`mjtJoint.mjJNT_HINGE` ...).
 Anything else raises at the call that asks for it.
 
@@ -27,8 +27,9 @@ from typing import Callable
 
 import numpy as np
 
-from .compiler.mjcf import (_GEOM_DEFAULTS, _JOINT_DEFAULTS, _SITE_DEFAULTS, XBody, XGeom,
-                            XJoint, XModel, XSite, parse_mjcf_string, quat_normalize)
+from .compiler.mjcf import (_EQUALITY_DEFAULTS, _GEOM_DEFAULTS, _JOINT_DEFAULTS, _SITE_DEFAULTS,
+                            EQUALITY_KINDS, XBody, XEquality, XGeom, XJoint, XModel, XSite,
+                            parse_mjcf_string, quat_normalize)
 from .compiler.model import (SENSOR_NAME_ATTRS, ActuatorSpec, EntitySpec, Model,
                              compile_scene)
 
@@ -40,6 +41,10 @@ class mjtJoint:  # noqa: N801 - MuJoCo's enum names
 class mjtGeom:  # noqa: N801
   mjGEOM_PLANE, mjGEOM_HFIELD, mjGEOM_SPHERE, mjGEOM_CAPSULE = 0, 1, 2, 3
   mjGEOM_ELLIPSOID, mjGEOM_CYLINDER, mjGEOM_BOX, mjGEOM_MESH = 4, 5, 6, 7
+
+
+class mjtEq:  # noqa: N801
+  mjEQ_CONNECT, mjEQ_WELD, mjEQ_JOINT, mjEQ_TENDON, mjEQ_FLEX, mjEQ_DISTANCE = 0, 1, 2, 3, 4, 5
 
 
 class mjtLimited:  # noqa: N801
@@ -260,6 +265,30 @@ class SpecActuator:
                         inheritrange=float(self.inheritrange))
 
 
+class SpecEquality:
+  """`MjsEquality` subset: a joint equality.  `name1` / `name2` are the joints (`name2` empty:
+  `name1` alone is held at `data[0]`), `data` the five polynomial coefficients."""
+
+  type = mjtEq.mjEQ_JOINT
+
+  def __init__(self, x: XEquality):
+    self._x = x
+
+  name = property(lambda self: self._x.name, lambda self, v: setattr(self._x, "name", v))
+  name1 = property(lambda self: self._x.attrs["joint1"],
+                   lambda self, v: self._x.attrs.__setitem__("joint1", str(v)))
+  name2 = property(lambda self: self._x.attrs.get("joint2") or "",
+                   lambda self, v: self._x.attrs.__setitem__("joint2", str(v) if v else None))
+  data = property(lambda self: np.array(self._x.attrs["polycoef"], float),
+                  lambda self, v: self._x.attrs.__setitem__("polycoef", _vec(v, 5)))
+  solref = property(lambda self: np.array(self._x.attrs["solref"], float),
+                    lambda self, v: self._x.attrs.__setitem__("solref", _vec(v, 2)))
+  solimp = property(lambda self: np.array(self._x.attrs["solimp"], float),
+                    lambda self, v: self._x.attrs.__setitem__("solimp", _vec(v, 5)))
+  active = property(lambda self: str(self._x.attrs.get("active", "true")).lower() != "false",
+                    lambda self, v: self._x.attrs.__setitem__("active", "true" if v else "false"))
+
+
 @dataclass
 class SpecKey:
   name: str
@@ -351,6 +380,42 @@ class Spec:
     self.actuators.append(a)
     return a
 
+  @property
+  def equalities(self) -> list[SpecEquality]:
+    return [SpecEquality(e) for e in self._xml.equalities]
+
+  def equality(self, name: str) -> SpecEquality:
+    for e in self.equalities:
+      if e.name == name:
+        return e
+    raise KeyError(f"no equality '{name}'")
+
+  def add_equality(self, name: str = "", type: int = mjtEq.mjEQ_JOINT, name1: str = "",
+                   name2: str = "", data=None, solref=None, solimp=None,
+                   active: bool = True) -> SpecEquality:
+    """`MjSpec.add_equality`: a joint equality between joints `name1` and `name2` (empty:
+    `name1` alone); `data` = polycoef, at most five values (the rest keep MuJoCo's defaults)."""
+    if int(type) != mjtEq.mjEQ_JOINT:
+      raise NotImplementedError(f"{EQUALITY_KINDS[int(type)]} equalities (only joint equalities "
+                                "are computed)")
+    if not name1:
+      raise ValueError("add_equality: name1 (the first joint) is required")
+    attrs = dict(_EQUALITY_DEFAULTS, joint1=str(name1), joint2=str(name2) if name2 else None)
+    x = XEquality(name, attrs)
+    eq = SpecEquality(x)
+    if data is not None:
+      pc = _vec(data)
+      if len(pc) > 5:
+        raise ValueError(f"add_equality: data takes at most 5 polynomial coefficients, got {len(pc)}")
+      attrs["polycoef"] = pc + _EQUALITY_DEFAULTS["polycoef"][len(pc):]
+    if solref is not None:
+      eq.solref = solref
+    if solimp is not None:
+      eq.solimp = solimp
+    eq.active = active
+    self._xml.equalities.append(x)
+    return eq
+
   def add_key(self, name: str = "", qpos=None, ctrl=None) -> SpecKey:
     k = SpecKey(name, np.asarray(qpos if qpos is not None else [], float),
                 np.asarray(ctrl if ctrl is not None else [], float))
@@ -362,13 +427,15 @@ class Spec:
       self.keys.remove(obj)
     elif isinstance(obj, SpecActuator):
       self.actuators.remove(obj)
+    elif isinstance(obj, SpecEquality):
+      self._xml.equalities[:] = [e for e in self._xml.equalities if e is not obj._x]
     else:
       raise NotImplementedError(f"delete {type(obj).__name__}")
 
   def attach(self, child: "Spec", prefix: str = "", frame: SpecFrame | None = None) -> None:
     """`MjSpec.attach`: the child's world children (bodies, world geoms / sites) hang off
-    `frame` (default: this world body) with every name prefixed; actuators and sensors come
-    along, retargeted.  Keyframes do not (MuJoCo: delete them first, re-add on the parent)."""
+    `frame` (default: this world body) with every name prefixed; actuators, sensors and
+    equalities come along, retargeted.  Keyframes do not (MuJoCo: delete them first, re-add on the parent)."""
     if child.keys:
       raise ValueError("attach: the child spec still has keyframes")
     src = copy.deepcopy(child._xml)
@@ -403,6 +470,10 @@ class Spec:
     for tag, attrs in src.sensors:
       self._xml.sensors.append((tag, {k: (prefix + v if k in SENSOR_NAME_ATTRS + ("name",) and v != "world"
                                           else v) for k, v in attrs.items()}))
+    for e in src.equalities:
+      a = dict(e.attrs, joint1=prefix + e.attrs["joint1"],
+               joint2=prefix + e.attrs["joint2"] if e.attrs.get("joint2") else None)
+      self._xml.equalities.append(XEquality(prefix + e.name if e.name else e.name, a))
     for a in child.actuators:
       b = copy.deepcopy(a)
       b.name, b.target = prefix + a.name, prefix + a.target
