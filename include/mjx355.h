@@ -139,6 +139,17 @@ typedef struct mjxModelDesc_ {
   int neq;
   const int32_t *eq_type, *eq_obj1id, *eq_obj2id, *eq_active0;
   const double *eq_data /*5*/, *eq_solref /*2*/, *eq_solimp /*5*/;
+  /* Torsional and rolling friction (appended).  geom_condim is 1, 3, 4 or 6 (mjx_model_create
+   * refuses any other): a contact of dimension dim > 1 has 2 (dim - 1) pyramid rows, pair k of
+   * them J_n +/- mu_k J_k with mu = (f0, f0, f1, f2, f2) of the mixed geom_friction, J_0 / J_1
+   * the relative linear velocity along the tangents, J_2 the relative angular velocity (body 2
+   * minus body 1) along the normal and J_3 / J_4 along the tangents.  max_condim is the largest
+   * geom_condim, or 0 to have it derived (any other value that is not the largest is refused).
+   * A model with max_condim > 3 runs the generic kernels, its contacts count 2 (max_condim - 1)
+   * rows in every capacity (mjx_sim_create_ex refuses an njmax_max below one such contact), and
+   * the data field "contact_torque" [nworld, nconmax, 3] holds (torsional, rolling 1, rolling 2)
+   * in the contact frame, zero for contacts of dimension <= 3. */
+  int max_condim;
 } mjxModelDesc;
 
 size_t mjx_model_desc_size(void); /* sizeof(mjxModelDesc): ABI check for FFI bindings */

@@ -93,15 +93,17 @@ struct Capacity {
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
 static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid, int neq,
-                         const char* too_big, Capacity& c) {
+                         int max_condim, const char* too_big, Capacity& c) {
   c.d = d;
   for (int i = 0; i < 3; i++) {
-    c.lds[i] = mjx::make_lds(d, i);
+    // (phases A and C hold the contacts' friction coefficients: five each with torsional or
+    // rolling contacts in the model)
+    c.lds[i] = mjx::make_lds(d, i, false, mjx::con_mu_width(max_condim));
     if ((size_t)c.lds[i].total * 4 > 160 * 1024) return fail(too_big);
   }
   // a model with joint equalities runs the generic kernels: no specialisation holds the
-  // equality rows' code (engine_impl.h neq_of)
-  c.spec = neq > 0 ? 0 : mjx::find_spec(d, dof_parentid.data());
+  // equality rows' code (engine_impl.h neq_of), and none the rotational contact rows' (condim_of)
+  c.spec = neq > 0 || max_condim > 3 ? 0 : mjx::find_spec(d, dof_parentid.data());
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -306,6 +308,7 @@ int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
   // the derived tables
   dm.nmaskword = t.nmaskword;
   dm.neq = t.neq;
+  dm.max_condim = t.max_condim;
   dm.ncsens = t.ncsens;
   const size_t nmask = (size_t)desc->nmaskword * d.nsensor;
   if (upload(m.get(), t.dof_ancmask, dm.dof_ancmask) || upload(m.get(), t.body_submask, dm.body_submask) ||
@@ -349,6 +352,9 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   if (njmax <= 0) return fail("njmax must be positive");
   if (njmax < 2 * model->t.neq)
     return fail("njmax below the model's equality rows (two per equality constraint)");
+  if (model->t.max_condim > 3 && njmax_max < 2 * model->t.neq + 2 * (model->t.max_condim - 1))
+    return fail("njmax_max below one contact of the model's largest condim (2 (condim - 1) rows "
+                "behind the equality rows)");
   if (nconmax_max < nconmax || nconmax_max > mjx::kMaxContacts || njmax_max < njmax)
     return fail("max capacity: nconmax <= nconmax_max <= 512 and njmax <= njmax_max");
   if (nconmax_max > mjx::kWave && nconmax_max > njmax_max)
@@ -363,7 +369,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   mjx::Dims dims = model->t.d;
   dims.nconmax = nconmax;
   dims.njmax = njmax;
-  if (make_capacity(dims, model->t.dof_parentid, model->t.neq,
+  if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
                     "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
   s->nrowclass = mjx::choose_row_classes(s->fast.d, s->fast.spec, s->row_cap);
@@ -384,7 +390,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   if (s->has_big) {
     dims.nconmax = nconmax_max;
     dims.njmax = njmax_max;
-    if (make_capacity(dims, model->t.dof_parentid, model->t.neq,
+    if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
                       "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed
@@ -441,6 +447,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   reserve("__evtotal", sizeof(int32_t) * 4);
   reserve("__prof", sizeof(unsigned long long) * 48);
   reserve("__wtrace", sizeof(unsigned long long) * 8 * (size_t)nworld);
+  reserve("contact_torque", sizeof(float) * (size_t)nworld * d.nconmax * 3);
   if (device_zeros(&s->fast.gscr, sizeof(float) * (size_t)nworld * s->fast.gstride, "scratch") ||
       device_zeros(&s->wl, sizeof(int) * ((size_t)nworld + 2 * (mjx::kRowClasses + 1) * mjx::kMaxSplit),
                    "work lists"))
@@ -491,6 +498,11 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   s->dd.wtrace = (unsigned long long*)(base + offs[k++].second);
   s->fields["world_trace"] = FieldInfo{s->dd.wtrace, false, 16, 1, true, false};
   s->names.push_back("world_trace");
+  // torsional / rolling contact torque in the contact frame, beside contact_force (the pointer
+  // travels in the sim's model copy: engine.h DModel)
+  s->dm.contact_torque = (float*)(base + offs[k++].second);
+  s->fields["contact_torque"] = FieldInfo{s->dm.contact_torque, true, (int64_t)d.nconmax, 3, true, false, false};
+  s->names.push_back("contact_torque");
   // model fields visible as "model.<name>"
   for (auto& kv : model->float_dims) {
     FieldInfo fi{nullptr, true, kv.second.first, kv.second.second, false, true};

@@ -42,7 +42,11 @@ constexpr int ltr_size(int nvp) { return 8 * (nvp >> 2) * ((nvp >> 2) + 1); }
 // jglobal (phase B only): the Newton reads the constraint Jacobian straight from the B pack in
 // global memory (L2) instead of an LDS copy -- the carve of the latency Newton kernel's heavy
 // worlds, whose J (up to njmax x nvp floats) is most of the full-capacity carve
-constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false) {
+// mu_w: friction coefficients kept per contact (con_mu_width: 2, or 5 for a model with
+// torsional / rolling contacts; no other slot depends on it, so every carve of a model without
+// such contacts is what it was)
+constexpr int con_mu_width(int max_condim) { return max_condim > 3 ? 5 : 2; }
+constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false, int mu_w = 2) {
   Lds L{};
   const int nb = d.nbody, nv = (d.nv + 3) & ~3, C = d.nconmax, R = d.njmax;  // nv padded
   constexpr int A = 1, B = 2, Cp = 4;
@@ -80,7 +84,7 @@ constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false) {
     {&Lds::con_g1, C, A | Cp}, {&Lds::con_g2, C, A | Cp}, {&Lds::con_key, C, A},
     {&Lds::con_dist, C, A | Cp}, {&Lds::con_pos, 3 * C, A | Cp}, {&Lds::con_frame, 9 * C, 0},
     {&Lds::con_n, 3 * C, A | Cp},  // unit normals: cframe() rebuilds the frame where used
-    {&Lds::con_mu, 2 * C, A | Cp}, {&Lds::con_kb, 2 * C, A}, {&Lds::con_imp, C, A},
+    {&Lds::con_mu, mu_w * C, A | Cp}, {&Lds::con_kb, 2 * C, A}, {&Lds::con_imp, C, A},
     {&Lds::con_imargin, C, A}, {&Lds::con_dim, C, A | Cp}, {&Lds::con_efc, C, A | Cp},
     {&Lds::efc_J, ph == 1 && jglobal ? 0 : R * nv, B},  // phase A writes J rows straight into the B pack
     {&Lds::efc_aref, R, A | B}, {&Lds::efc_D, R, A | B}, {&Lds::efc_jar, R, B},

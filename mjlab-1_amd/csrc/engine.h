@@ -120,7 +120,18 @@ struct DModel {
 #undef X_INT
 #undef X_FLT
   int neq;
-  int eq_reserved[12];
+  // Torsional / rolling friction (contact dimensions 4 and 6), in the same block for the same
+  // reason: no specialisation has such a geom, so their kernels take the largest contact
+  // dimension as the constant 3 (engine_impl.h condim_of) and hold none of the rotational rows'
+  // code, and only the generic kernels (and the reset) touch the torque output.  max_condim is
+  // the largest geom_condim of the model; with max_condim > 3 the carves keep five friction
+  // coefficients per contact instead of two (carve.h con_mu_width).  contact_torque is
+  // [nworld][con_stride][3], the per-sim output beside DData::contact_force (it lives here, in
+  // the sim's copy of the model, so that DData and everything behind it keep their offsets).
+  int max_condim;
+  int eq_reserved0;
+  float* contact_torque;
+  int eq_reserved[8];
 };
 static_assert(sizeof(DModel) - offsetof(DModel, eq_type) == 128, "DModel: the equality block is 128 bytes");
 

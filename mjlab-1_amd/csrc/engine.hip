@@ -49,6 +49,8 @@ __global__ void reset_kernel(Dims d, DModel m, DData D, const uint8_t* mask, int
     for (int t = 0; t < 3; t++) D.contact_pos[(wc + c) * 3 + t] = 0.f;
     for (int t = 0; t < 9; t++) D.contact_frame[(wc + c) * 9 + t] = 0.f;
     for (int t = 0; t < 3; t++) D.contact_force[(wc + c) * 3 + t] = 0.f;
+    if (m.max_condim > 3)  // (never written otherwise: zero since the allocation)
+      for (int t = 0; t < 3; t++) m.contact_torque[(wc + c) * 3 + t] = 0.f;
   }
   __syncthreads();
   if (lane == 0) { D.time[w] = 0; D.ncon[w] = 0; D.nefc[w] = 0; wsv[6] = 0; wsv[7] = 0; }

@@ -1314,15 +1314,44 @@ __device__ __forceinline__ EqRow eq_row(const DModel& m, const float* eq_data, c
 // con_dim holds the contact's condim, or 0 for a contact in its gap (margin - gap <= dist <
 // margin; mjContact.exclude = 1): it stays in the contact list, has no rows and no force
 __device__ __forceinline__ int con_nrows(int cd) { return cd <= 1 ? cd : 2 * (cd - 1); }
-// contact c's force in its frame (normal, two tangents) from its rows' forces
-__device__ __forceinline__ V3 con_frame_force(const float* S, const int* Si, const Lds& L, int c) {
+// a contact dimension whose rows phase A does not write (counted as an unsupported pair): any
+// but 0, 1, 3 and -- in a model with such geoms (mcd > 3) -- 4 and 6; model creation refuses
+// them, so this guards a model field rewritten later
+__device__ __forceinline__ bool con_dim_unsupported(int cd, int mcd) {
+  return cd > 1 && cd != 3 && !(mcd > 3 && (cd == 4 || cd == 6));
+}
+// contact c's force in its frame (normal, two tangents) from its rows' forces.  mcd: the
+// model's largest contact dimension (condim_of: the constant 3 in a specialised kernel, whose
+// code is then what it was); a contact keeps con_mu_width(mcd) friction coefficients, and one
+// of dimension 4 / 6 adds its 2 / 6 rotational rows to the normal force.
+__device__ __forceinline__ V3 con_frame_force(const float* S, const int* Si, const Lds& L, int c,
+                                              int mcd) {
   const int cd = Si[L.con_dim + c];
   if (cd == 0) return V3{0, 0, 0};
   const int r0 = Si[L.con_efc + c];
   if (cd == 1) return V3{S[L.efc_force + r0], 0, 0};
+  const int muw = con_mu_width(mcd);
   const float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
   const float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
-  return V3{e0 + e1 + e2 + e3, (e0 - e1) * S[L.con_mu + 2 * c], (e2 - e3) * S[L.con_mu + 2 * c + 1]};
+  float fn = e0 + e1 + e2 + e3;
+  if (mcd > 3 && cd > 3)
+    for (int r = 4; r < 2 * (cd - 1); r++) fn += S[L.efc_force + r0 + r];
+  return V3{fn, (e0 - e1) * S[L.con_mu + muw * c], (e2 - e3) * S[L.con_mu + muw * c + 1]};
+}
+// ... and its torque in that frame (torsional about the normal, rolling about the two
+// tangents): component k - 2 = mu_k (f_2k - f_2k+1), zero below dimension 4 (6 for rolling)
+__device__ __forceinline__ V3 con_frame_torque(const float* S, const int* Si, const Lds& L, int c) {
+  const int cd = Si[L.con_dim + c];
+  V3 t = {0, 0, 0};
+  if (cd <= 3) return t;
+  const float* e = S + L.efc_force + Si[L.con_efc + c];
+  const float* mu = S + L.con_mu + 5 * c;
+  t.x = mu[2] * (e[4] - e[5]);
+  if (cd == 6) {
+    t.y = mu[3] * (e[6] - e[7]);
+    t.z = mu[4] * (e[8] - e[9]);
+  }
+  return t;
 }
 
 // --------------------------------------------------------------------------- specialisation
@@ -1374,6 +1403,14 @@ template <int SP>
 __device__ __forceinline__ int neq_of(const Params* P) {
   if constexpr (SP > 0) return 0;
   else return P->m.neq;
+}
+// The model's largest contact dimension: 3 in every specialisation (no specs.inc entry or
+// run-time specialisation has a torsional or rolling contact: capi.cpp make_capacity), so the
+// rotational rows of phases A and C fold away there; the generic kernels read it.
+template <int SP>
+__device__ __forceinline__ int condim_of(const Params* P) {
+  if constexpr (SP > 0) return 3;
+  else return P->m.max_condim;
 }
 template <int SP, int K>
 __device__ __forceinline__ decltype(auto) lds_of(const Params* P) {
@@ -1910,10 +1947,11 @@ __device__ __forceinline__ V3 point_vel_r(const float* S, const Lds& L, int b, i
 __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* Si, const Lds& L,
                                                      const DModel& m, const Dims& d, float* sd,
                                                      int ncon, int maxmatch, bool all,
-                                                     const Params* __restrict__ P, int lane) {
+                                                     const Params* __restrict__ P, int lane,
+                                                     int mcd) {
   const int c = lane;
   const bool valid = c < ncon;
-  V3 fg = {0, 0, 0}, fc = {0, 0, 0};
+  V3 fg = {0, 0, 0}, fc = {0, 0, 0}, tc = {0, 0, 0};  // tc: torque (mcd > 3 only)
   float dist = 0.f;
   // the sensors this contact matches, all at once: bit k of m1 (m2) = sensor k with the
   // contact's geom 1 (geom 2) as its primary (geom_csmask1/2, host-derived)
@@ -1924,8 +1962,9 @@ __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* 
     m2 = m.geom_csmask1[g2] & m.geom_csmask2[g1];
     if (all) {  // (before the last substep only found counts are computed: no forces)
       dist = S[L.con_dist + c];
-      fc = con_frame_force(S, Si, L, c);
+      fc = con_frame_force(S, Si, L, c, mcd);
       fg = frame_tv(S + L.con_n + 3 * c, fc);
+      if (mcd > 3) tc = con_frame_torque(S, Si, L, c);
     }
   }
   // the sensors' descriptors, lane k = k-th single-slot contact sensor (ncsens <= 64): the
@@ -2007,6 +2046,9 @@ __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* 
         else if (bits & 2) {
           const float fx = rl(fc.x, cs), fy = rl(fc.y, cs), fz = rl(fc.z, cs);
           v = lane == 0 ? fx : lane == 1 ? fy : lane == 2 ? fz : 0.f;
+        } else if (mcd > 3 && (bits & 4)) {  // the contact-frame torque, as the force
+          const float tx = rl(tc.x, cs), ty = rl(tc.y, cs), tz = rl(tc.z, cs);
+          v = lane == 0 ? tx : lane == 1 ? ty : lane == 2 ? tz : 0.f;
         }
       }
     }
@@ -2070,6 +2112,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   const Opt& o = P->o;
   const DModel& m = P->m;
   const DData& D = P->D;
+  // largest contact dimension and the friction coefficients a contact keeps (constants 3 and 2
+  // in a specialised kernel)
+  const int mcd = condim_of<SP>(P);
+  const int muw = con_mu_width(mcd);
   // phase B: `integrate` carries the Newton row class (0 = full capacity, k > 0 = LP[2 + k])
   constexpr bool JG = PH == 1 && (LAT & 2) != 0;
   constexpr bool NET = PH == 0 && (LAT & 4) != 0;
@@ -2968,18 +3014,19 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const float* ggap = MF(geom_gap);
         int p1 = m.geom_priority[g1], p2 = m.geom_priority[g2];
         int dim;
-        float f0, f1;
+        float f0, f1, f2;
         float sr[2], si[5];
         if (p1 != p2) {
           int g = p1 > p2 ? g1 : g2;
           dim = m.geom_condim[g];
-          f0 = fri[3 * g]; f1 = fri[3 * g + 1];
+          f0 = fri[3 * g]; f1 = fri[3 * g + 1]; f2 = fri[3 * g + 2];
           sr[0] = sref[2 * g]; sr[1] = sref[2 * g + 1];
           for (int i = 0; i < 5; i++) si[i] = simp[5 * g + i];
         } else {
           dim = max(m.geom_condim[g1], m.geom_condim[g2]);
           f0 = fmaxf(fri[3 * g1], fri[3 * g2]);
           f1 = fmaxf(fri[3 * g1 + 1], fri[3 * g2 + 1]);
+          f2 = fmaxf(fri[3 * g1 + 2], fri[3 * g2 + 2]);
           float s1 = smix[g1], s2 = smix[g2], mix;
           if (s1 < MINVAL && s2 < MINVAL) mix = 0.5f;
           else if (s1 < MINVAL) mix = 0.f;
@@ -2996,9 +3043,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           }
           for (int i = 0; i < 5; i++) si[i] = mix * simp[5 * g1 + i] + (1 - mix) * simp[5 * g2 + i];
         }
-        (void)f1;
-        S[L.con_mu + 2 * c] = fmaxf(MINMU, f0);
-        S[L.con_mu + 2 * c + 1] = fmaxf(MINMU, f0);
+        // the pyramid's friction (f0, f0, f1, f2, f2), every component floored; a model
+        // without torsional or rolling contacts keeps the two sliding coefficients only
+        S[L.con_mu + muw * c] = fmaxf(MINMU, f0);
+        S[L.con_mu + muw * c + 1] = fmaxf(MINMU, f0);
+        if (mcd > 3) {
+          S[L.con_mu + muw * c + 2] = fmaxf(MINMU, f1);
+          S[L.con_mu + muw * c + 3] = fmaxf(MINMU, f2);
+          S[L.con_mu + muw * c + 4] = fmaxf(MINMU, f2);
+        } else {
+          (void)f1; (void)f2;
+        }
         const float cmargin = fmaxf(gmar[g1], gmar[g2]);
         const float imargin = cmargin - fmaxf(ggap[g1], ggap[g2]);
         // in its gap (margin - gap <= dist < margin): kept, without rows (con_nrows); the band is
@@ -3131,14 +3186,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       if (con1) {
         cdim = lane < ncon ? Si[L.con_dim + lane] : 0;
         crow = lane < ncon ? con_nrows(cdim) : 0;
-        if (lane < ncon && cdim > 1 && cdim != 3) atomicOr(&ints[3], 4);
+        if (lane < ncon && con_dim_unsupported(cdim, mcd)) atomicOr(&ints[3], 4);
         con_off = wave_excl_scan(crow, lane, &con_total);
       } else {
         for (int c0 = 0; c0 < ncon; c0 += kWave) {
           const int c = c0 + lane;
           const int cd = c < ncon ? Si[L.con_dim + c] : 0;
           const int cr = c < ncon ? con_nrows(cd) : 0;
-          if (c < ncon && cd > 1 && cd != 3) atomicOr(&ints[3], 4);
+          if (c < ncon && con_dim_unsupported(cd, mcd)) atomicOr(&ints[3], 4);
           int tot, off = wave_excl_scan(cr, lane, &tot);
           if (c < ncon) Si[L.con_efc + c] = con_total + off;
           con_total += tot;
@@ -3253,12 +3308,14 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       const int ngrp = nvp <= kWave / 2 ? kWave / nvp : 1;
       const int grp = lane / nvp;
       // element i of contact c's rows, from the contact's values (both loops below)
+      // (mur: the torsional and the two rolling coefficients, read for dim > 3 only)
       auto con_jrows = [&](int i, uint64_t bm, V3 cang, V3 clin, int cb, V3 pos, V3 com1, V3 com2,
-                           const CFrame& F, int dim, int r0, float mu0, float mu1) {
+                           const CFrame& F, int dim, int r0, float mu0, float mu1, V3 mur) {
         const int b1 = cb_b1(cb), b2 = cb_b2(cb);
+        const bool in2 = b2 > 0 && ((bm >> b2) & 1ull), in1 = b1 > 0 && ((bm >> b1) & 1ull);
         V3 jd = {0, 0, 0};
-        if (b2 > 0 && ((bm >> b2) & 1ull)) jd = jd + clin + cross(cang, pos - com2);
-        if (b1 > 0 && ((bm >> b1) & 1ull)) jd = jd - (clin + cross(cang, pos - com1));
+        if (in2) jd = jd + clin + cross(cang, pos - com2);
+        if (in1) jd = jd - (clin + cross(cang, pos - com1));
         float jn = dot(F.n, jd);
         if (dim == 1) {
           Jg[r0 * nvp + i] = jn;
@@ -3269,6 +3326,24 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           Jg[(r0 + 1) * nvp + i] = jn - mu0 * jt1;
           Jg[(r0 + 2) * nvp + i] = jn + mu1 * jt2;
           Jg[(r0 + 3) * nvp + i] = jn - mu1 * jt2;
+          // rotational rows (dim wave-uniform in the register-fed loop): the dof's share of the
+          // relative angular velocity, body 2 minus body 1, along the normal (torsional) and
+          // the two tangents (rolling)
+          if (mcd > 3 && dim > 3) {
+            V3 wd = {0, 0, 0};
+            if (in2) wd = wd + cang;
+            if (in1) wd = wd - cang;
+            const float jr0 = dot(F.n, wd);
+            Jg[(r0 + 4) * nvp + i] = jn + mur.x * jr0;
+            Jg[(r0 + 5) * nvp + i] = jn - mur.x * jr0;
+            if (dim == 6) {
+              const float jr1 = dot(F.t, wd), jr2 = dot(F.b, wd);
+              Jg[(r0 + 6) * nvp + i] = jn + mur.y * jr1;
+              Jg[(r0 + 7) * nvp + i] = jn - mur.y * jr1;
+              Jg[(r0 + 8) * nvp + i] = jn + mur.z * jr2;
+              Jg[(r0 + 9) * nvp + i] = jn - mur.z * jr2;
+            }
+          }
         }
       };
       // element i of equality row r (payload e): two dof entries, not the limit's one
@@ -3285,13 +3360,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const int i = lane;
         int kcb = 0, kdim = 0, kr0 = 0;
         float kmu0 = 0, kmu1 = 0;
+        V3 kmur = {0, 0, 0};  // torsional / rolling coefficients: lane registers of the generic kernels only
         V3 kpos = {0, 0, 0}, kc1 = {0, 0, 0}, kc2 = {0, 0, 0};
         CFrame kF = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
         if (lane < ncon) {
           kcb = Si[L.con_key + lane];
           kdim = cdim;
           kr0 = lim_total + con_off;
-          kmu0 = S[L.con_mu + 2 * lane]; kmu1 = S[L.con_mu + 2 * lane + 1];
+          kmu0 = S[L.con_mu + muw * lane]; kmu1 = S[L.con_mu + muw * lane + 1];
+          if constexpr (SP == 0) {
+            if (mcd > 3) kmur = v3(S + L.con_mu + muw * lane + 2);
+          }
           kpos = v3(S + L.con_pos + 3 * lane);
           kF = cframe(v3(S + L.con_n + 3 * lane));
           kc1 = v3(S + L.subtree_com + 3 * cb_r1(kcb));
@@ -3321,7 +3400,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           const float mu0 = rl(kmu0, c), mu1 = rl(kmu1, c);
           const V3 pos = rl3(kpos, c), com1 = rl3(kc1, c), com2 = rl3(kc2, c);
           const CFrame F = {rl3(kF.n, c), rl3(kF.t, c), rl3(kF.b, c)};
-          if (i < nv) con_jrows(i, bm, cang, clin, cb, pos, com1, com2, F, dim, r0, mu0, mu1);
+          V3 mur = {0, 0, 0};
+          if constexpr (SP == 0) {
+            if (mcd > 3 && dim > 3) mur = rl3(kmur, c);
+          }
+          if (i < nv) con_jrows(i, bm, cang, clin, cb, pos, com1, com2, F, dim, r0, mu0, mu1, mur);
         }
       } else
       for (int i = lane - grp * nvp; grp < ngrp && i < nvp; i += kWave) {
@@ -3343,7 +3426,8 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           con_jrows(i, bm, cang, clin, cb, v3(S + L.con_pos + 3 * c),
                     v3(S + L.subtree_com + 3 * cb_r1(cb)), v3(S + L.subtree_com + 3 * cb_r2(cb)),
                     cframe(v3(S + L.con_n + 3 * c)), Si[L.con_dim + c], Si[L.con_efc + c],
-                    S[L.con_mu + 2 * c], S[L.con_mu + 2 * c + 1]);
+                    S[L.con_mu + muw * c], S[L.con_mu + muw * c + 1],
+                    mcd > 3 ? v3(S + L.con_mu + muw * c + 2) : V3{0, 0, 0});
         }
       }
       sync();
@@ -3377,8 +3461,12 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (type == EFC_FRICTIONLESS) {
             diag = tran;
           } else {
-            float mu = S[L.con_mu + 2 * c + ((r - Si[L.con_efc + c]) >> 1)];
-            diag = (tran + mu * mu * tran) / o.impratio;
+            const int k = (r - Si[L.con_efc + c]) >> 1;
+            float mu = S[L.con_mu + muw * c + k];
+            // pairs 2..4 (torsional, rolling) weigh the bodies' rotational inverse inertia
+            float wk = tran;
+            if (mcd > 3 && k >= 2) wk = binvw[2 * cb_b1(cb) + 1] + binvw[2 * cb_b2(cb) + 1];
+            diag = (tran + mu * mu * wk) / o.impratio;
           }
           imp = S[L.con_imp + c];
           K = S[L.con_kb + 2 * c];
@@ -3401,9 +3489,19 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           vel = dot(F.n, v);
           if (type != EFC_FRICTIONLESS) {
             int kr = r - Si[L.con_efc + c];
-            const V3 t = (kr >> 1) ? F.b : F.t;
-            float mu = S[L.con_mu + 2 * c + (kr >> 1)];
-            vel += ((kr & 1) ? -mu : mu) * dot(t, v);
+            float mu = S[L.con_mu + muw * c + (kr >> 1)];
+            if (mcd > 3 && kr >= 4) {
+              // the relative angular velocity (the angular part of cvel; the world's is zero)
+              const int b1 = cb_b1(cb), b2 = cb_b2(cb);
+              V3 wr = {0, 0, 0};
+              if (b2 > 0) wr = wr + v3(S + L.cvel + 6 * b2);
+              if (b1 > 0) wr = wr - v3(S + L.cvel + 6 * b1);
+              const V3 ax = (kr >> 1) == 2 ? F.n : (kr >> 1) == 3 ? F.t : F.b;
+              vel += ((kr & 1) ? -mu : mu) * dot(ax, wr);
+            } else {
+              const V3 t = (kr >> 1) ? F.b : F.t;
+              vel += ((kr & 1) ? -mu : mu) * dot(t, v);
+            }
           }
         }
         S[L.efc_D + r] = 1.0f / Rr;
@@ -3477,7 +3575,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          const V3 f = con_frame_force(S, Si, L, c);
+          const V3 f = con_frame_force(S, Si, L, c, mcd);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -3503,8 +3601,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              const V3 f = con_frame_force(S, Si, L, c);
+              const V3 f = con_frame_force(S, Si, L, c, mcd);
               oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
+            } else if (mcd > 3 && (bits & 4)) {
+              const V3 t = con_frame_torque(S, Si, L, c);
+              oo[0] = t.x; oo[1] = t.y; oo[2] = t.z;
             }
           }
         }
@@ -3604,7 +3705,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       cp4(gc + LC.con_dist, S + L.con_dist, C4, lane);
       cp4(gc + LC.con_pos, S + L.con_pos, (3 * C + 3) & ~3, lane);
       cp4(gc + LC.con_n, S + L.con_n, (3 * C + 3) & ~3, lane);  // normals (C rebuilds frames)
-      cp4(gc + LC.con_mu, S + L.con_mu, (2 * C + 3) & ~3, lane);
+      cp4(gc + LC.con_mu, S + L.con_mu, (muw * C + 3) & ~3, lane);
       cp4(gc + LC.con_dim, S + L.con_dim, C4, lane);
       cp4(gc + LC.con_efc, S + L.con_efc, C4, lane);
     }
@@ -4114,7 +4215,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          const V3 f = con_frame_force(S, Si, L, c);
+          const V3 f = con_frame_force(S, Si, L, c, mcd);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -4140,8 +4241,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              const V3 f = con_frame_force(S, Si, L, c);
+              const V3 f = con_frame_force(S, Si, L, c, mcd);
               oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
+            } else if (mcd > 3 && (bits & 4)) {
+              const V3 t = con_frame_torque(S, Si, L, c);
+              oo[0] = t.x; oo[1] = t.y; oo[2] = t.z;
             }
           }
         }
@@ -4149,7 +4253,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     }
     if (kCon1<SP> || ncon <= kWave)
       contact_sensors_wave(S, Si, L, m, d, D.sensordata + (size_t)w * d.nsensordata, ncon,
-                           o.maxmatch, last || P->outputs_every, P, lane);
+                           o.maxmatch, last || P->outputs_every, P, lane, mcd);
     st.stamp(11);
     if (last) {
       size_t wb = (size_t)w * nb;
@@ -4158,10 +4262,16 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       const int nout = min(P->con_stride, D.wstats[8 * (size_t)w + 6]);  // phase A's output slots
       for (int c = lane; c < nout; c += kWave) {
         V3 f = {0, 0, 0};
-        if (c < ncon && nefc > 0) f = con_frame_force(S, Si, L, c);
+        if (c < ncon && nefc > 0) f = con_frame_force(S, Si, L, c, mcd);
         D.contact_force[(wc + c) * 3] = f.x;
         D.contact_force[(wc + c) * 3 + 1] = f.y;
         D.contact_force[(wc + c) * 3 + 2] = f.z;
+        if (mcd > 3) {
+          V3 t = {0, 0, 0};
+          if (c < ncon && nefc > 0) t = con_frame_torque(S, Si, L, c);
+          float* ct = m.contact_torque + (wc + c) * 3;
+          ct[0] = t.x; ct[1] = t.y; ct[2] = t.z;
+        }
       }
     }
     // per-world counters, every substep (a fused multi-substep step must not lose the

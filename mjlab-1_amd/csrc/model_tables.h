@@ -23,6 +23,7 @@ struct ModelTables {
   Opt o{};
   int nmaskword = 0;
   int neq = 0;     // joint equalities (fields.h counts the eq_* fields by it)
+  int max_condim = 3;  // largest geom_condim, at least 3 (check_condims; engine.h DModel::max_condim)
   int ncsens = 0;  // 0 past 64 single-slot contact sensors (phase C then matches serially)
   std::vector<int32_t> dof_parentid;  // as given: find_spec checks a specialisation's dof tree
   // engine.h DModel, the host-derived part
@@ -168,6 +169,23 @@ inline std::string check_equalities(const mjxModelDesc& desc) {
       if (j >= 0 && desc.jnt_type[j] != JNT_HINGE && desc.jnt_type[j] != JNT_SLIDE)
         return who + "a joint equality takes hinge or slide joints";
   }
+  return "";
+}
+
+// Contact dimensions: 1 (frictionless), 3 (sliding), 4 (+ torsional) and 6 (+ rolling) have rows;
+// the descriptor's max_condim, where a host sets it, is the largest of them (0: derived here).
+inline std::string check_condims(const mjxModelDesc& desc, int& max_condim) {
+  max_condim = 3;
+  for (int g = 0; g < desc.ngeom; g++) {
+    const int cd = desc.geom_condim[g];
+    if (cd != 1 && cd != 3 && cd != 4 && cd != 6)
+      return "geom " + std::to_string(g) + ": condim " + std::to_string(cd) +
+             " is not supported (1, 3, 4 or 6)";
+    if (cd > max_condim) max_condim = cd;
+  }
+  if (desc.max_condim != 0 && std::max(desc.max_condim, 3) != max_condim)
+    return "max_condim " + std::to_string(desc.max_condim) + " is not the largest geom_condim (" +
+           std::to_string(max_condim) + ")";
   return "";
 }
 
@@ -418,6 +436,7 @@ inline void contact_sensor_masks(const mjxModelDesc& desc, ModelTables& t) {
 inline std::string build_model_tables(const mjxModelDesc& desc, ModelTables& t) {
   std::string err = tables::check_limits(desc);
   if (err.empty()) err = tables::check_equalities(desc);
+  if (err.empty()) err = tables::check_condims(desc, t.max_condim);
   if (err.empty()) err = tables::build_sensor_ext(desc, t.sensor_ext);
   if (err.empty() && desc.nmaskword < (desc.ngeom + 31) / 32) err = "nmaskword < ceil(ngeom / 32)";
   if (!err.empty()) return err;

@@ -62,7 +62,9 @@ class ModelDesc(ctypes.Structure):
   _fields_ = ([("abi_version", ctypes.c_int)] + [(n, ctypes.c_int) for n in _INT_SCALARS]
               + [(n, ctypes.c_double) for n in _REAL_SCALARS]
               + [("gravity", ctypes.c_double * 3)] + list(_ARRAYS)
-              + [("neq", ctypes.c_int)] + list(_EQ_ARRAYS))
+              + [("neq", ctypes.c_int)] + list(_EQ_ARRAYS)
+              # appended: the largest geom_condim (above 3: torsional / rolling contact rows)
+              + [("max_condim", ctypes.c_int)])
 
 
 _DTYPES = {_I: np.int32, _D: np.float64, _U64: np.uint64, _U32: np.uint32}
@@ -95,6 +97,8 @@ def make_desc(model) -> tuple[ModelDesc, list]:
   keep = []
   # (a model compiled without equalities carries no eq_* array: neq 0, the arrays unread)
   d.neq = int(len(model.arrays.get("eq_type", ())))
+  cd = np.asarray(model.arrays["geom_condim"]).reshape(-1)
+  d.max_condim = max(3, int(cd.max())) if cd.size else 3
   for name, ct in list(_ARRAYS) + _EQ_ARRAYS:
     if name == "sensor_cutoff":
       src = sensor_cutoff(model)

@@ -77,6 +77,7 @@ REFUSED_SENSORS = {
   "tendonactuatorfrc": "the compiler has no tendons",
   "e_potential": "the engine does not compute energies",
   "e_kinetic": "the engine does not compute energies"}
+SUPPORTED_CONDIM = (1, 3, 4, 6)
 CONTACT_FIELD_DIM = {"found": 1, "force": 3, "torque": 3, "dist": 1, "pos": 3, "normal": 3,
                      "tangent": 3}
 CONTACT_FIELD_BIT = {"found": 0, "force": 1, "torque": 2, "dist": 3, "pos": 4, "normal": 5,
@@ -252,6 +253,13 @@ class Model:
 
   def name2id(self, kind: str, name: str) -> int:
     return self.names[kind].index(name)
+
+  @property
+  def max_condim(self) -> int:
+    """Largest contact dimension of the geoms, at least 3: above 3 the model has torsional (4)
+    or rolling (6) contacts, whose contacts count 2 (max_condim - 1) rows in every capacity."""
+    cd = self.__dict__.get("arrays", {}).get("geom_condim", ())
+    return max(3, int(np.max(cd))) if len(cd) else 3
 
   @property
   def neq(self) -> int:
@@ -714,6 +722,11 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   m.names["geom"] = [g["name"] for g in geoms]
   A["geom_type"] = np.array([g["type"] for g in geoms], np.int32)
   A["geom_bodyid"] = np.array([g["body"] for g in geoms], np.int32)
+  # contact dimensions with rows: 1 frictionless, 3 sliding, 4 + torsional, 6 + rolling
+  for i, g in enumerate(geoms):
+    if g["condim"] not in SUPPORTED_CONDIM:
+      who = f"geom '{g['name']}'" if g["name"] else f"geom {i}"
+      raise ValueError(f"{who}: condim {g['condim']} is not supported (1, 3, 4 or 6)")
   for k in ("contype", "conaffinity", "condim", "priority"):
     A["geom_" + k] = np.array([g[k] for g in geoms], np.int32)
   for k in ("size", "pos", "quat", "friction", "solref", "solimp"):

@@ -181,6 +181,11 @@ def ensure_library(model, nconmax: int, njmax: int, role: int, compile_ok: bool 
   `wait_s`).  The library goes to the in-tree cache, or to ~/.cache/mjlab_amd/jit_cache when
   the package directory is read-only.  Raises RuntimeError when hipcc fails, OSError when no
   cache directory can be written."""
+  # torsional / rolling contact rows (condim 4 or 6) exist only in the generic kernels: such a
+  # model is never specialised (the engine would not select the library either)
+  cd = np.asarray(model.arrays.get("geom_condim", ())).reshape(-1)
+  if cd.size and int(cd.max()) > 3:
+    return None
   path, text, sid = library_path(model, nconmax, njmax, role)
   hit = _lookup(path)
   if hit is not None:

@@ -212,6 +212,19 @@ def _neq(model) -> int:
   return int(len(model.arrays.get("eq_type", ())))
 
 
+def _max_condim(model) -> int:
+  """Largest contact dimension of a compiled model's geoms, at least 3."""
+  cd = model.arrays.get("geom_condim", ())
+  return max(3, int(np.max(cd))) if len(cd) else 3
+
+
+def _contact_rows(model) -> int:
+  """Rows the capacities count per contact: the four of a sliding contact, or the
+  2 (max_condim - 1) of the model's largest torsional / rolling one (6 or 10)."""
+  mcd = _max_condim(model)
+  return 2 * (mcd - 1) if mcd > 3 else 4
+
+
 def world_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
   """Per-world contact/row capacities of the fast LDS carve."""
   if os.environ.get("MJX355_WORLD_CAPACITY"):  # diagnostic: "ncon,rows"
@@ -227,7 +240,7 @@ def world_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
     ncon, cap = int(min(64, max(ncon, 48))), 160
   rows = cfg.njmax if cfg.njmax is not None else cap
   # (two rows per joint equality: they come first and are never dropped)
-  rows = int(max(1, min(rows, 4 * ncon + 2 * nlim + 2 * _neq(model), cap)))
+  rows = int(max(1, min(rows, _contact_rows(model) * ncon + 2 * nlim + 2 * _neq(model), cap)))
   return ncon, rows
 
 
@@ -248,7 +261,7 @@ def max_capacity(cfg: SimulationCfg, model) -> tuple[int, int]:
   if os.environ.get("MJX355_RESOLVE", "1") == "0" or os.environ.get("MJX355_WORLD_CAPACITY"):
     return ncon, rows
   nlim = int(np.sum(model.jnt_limited)) if model.njnt else 0
-  rmax = int(cfg.njmax) if cfg.njmax is not None else 4 * 64 + 2 * nlim + 2 * _neq(model)
+  rmax = int(cfg.njmax) if cfg.njmax is not None else _contact_rows(model) * 64 + 2 * nlim + 2 * _neq(model)
   rmax = max(rows, rmax)
   cmax = min(rmax, MAX_CONTACTS)
   return max(ncon, cmax), rmax
@@ -290,7 +303,7 @@ def _warn_capacity(cfg: SimulationCfg, model, ncon: int, rows: int) -> None:
   # rows past 4 * ncon + 2 * (limited joints) cannot occur (every row belongs to a pyramidal
   # contact or a joint limit): warn only when the capacity is below what njmax allows of that
   nlim = int(np.sum(model.jnt_limited)) if model.njnt else 0
-  reachable = 4 * ncon + 2 * nlim + 2 * _neq(model)
+  reachable = _contact_rows(model) * ncon + 2 * nlim + 2 * _neq(model)
   if (cfg.njmax is not None and min(cfg.njmax, reachable) > rows) and asked not in _capacity_warned:
     _capacity_warned.add(asked)
     import warnings
@@ -314,6 +327,10 @@ class Simulation:
       raise NotImplementedError(
           "specialize='always': a model with equality constraints runs the generic kernels only "
           "(equalities are not compiled into specialised or JIT kernels)")
+    if cfg.specialize == "always" and _max_condim(model) > 3:
+      raise NotImplementedError(
+          "specialize='always': a model with torsional or rolling contacts (condim 4 or 6) runs "
+          "the generic kernels only (their rows are not compiled into specialised or JIT kernels)")
     dev = torch.device(device)
     if dev.type != "cuda":
       raise MjxError("mjlab_amd.Simulation runs only on a ROCm GPU (device 'cuda:N'); "
@@ -593,6 +610,9 @@ class Simulation:
     env = os.environ.get("MJX355_JIT")
     if env is not None:
       policy = "always" if env != "0" else "never"
+    if _max_condim(model) > 3:
+      # likewise the rotational contact rows (csrc/engine_impl.h condim_of)
+      return False
     if _neq(model) > 0:
       # equality rows exist only in the generic kernels (csrc/engine_impl.h neq_of): a
       # specialisation is neither looked up nor compiled, and jit.spec_dims never asked
