@@ -6,18 +6,13 @@
 // (lane per command body / joint, wave reductions); command updates, reference-state
 // initialisation and push run a thread per env; observations a thread per (env, element).
 // Failure-bin sampling statistics are one workgroup.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+#include <memory>
 
-#include <stdio.h>
-
-#include <string>
-
-#include "../../include/mjx355_task.h"
 #include "obs_hist.h"
+#include "task_common.h"
 
 namespace mjtr {
+using namespace mjxtc;
 
 constexpr int kPostEnvs = 16;
 
@@ -29,47 +24,15 @@ struct Acc {  // cross-env accumulators of one step's resets (block LDS copy, th
 };
 
 // ----------------------------------------------------------------------------- math
-// quaternions wxyz, as utils/lab_api/math.py (the torch helpers of mjlab_amd/math_utils.py)
-struct V3 { float x, y, z; };
-struct Q4 { float w, x, y, z; };
-__device__ __forceinline__ V3 v3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ Q4 q4(const float* p) { return {p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ float norm3(V3 a) { return sqrtf(dot(a, a)); }
-// quat_mul, math.py:526-563 (8-multiply order)
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  const float ww = (a.z + a.x) * (b.x + b.y), yy = (a.w - a.y) * (b.w + b.z);
-  const float zz = (a.w + a.y) * (b.w - b.z), xx = ww + yy + zz;
-  const float qq = 0.5f * (xx + (a.z - a.x) * (b.x - b.y));
-  return {qq - ww + (a.z - a.y) * (b.y - b.z), qq - xx + (a.x + a.w) * (b.x + b.w),
-          qq - yy + (a.w - a.x) * (b.y + b.z), qq - zz + (a.z + a.y) * (b.w - b.x)};
-}
 __device__ __forceinline__ Q4 qconj(Q4 q) { return {q.w, -q.x, -q.y, -q.z}; }
 // quat_inv: conjugate / max(|q|^2, eps)
 __device__ __forceinline__ Q4 qinv(Q4 q) {
   const float s = 1.0f / fmaxf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z, 1e-9f);
   return {q.w * s, -q.x * s, -q.y * s, -q.z * s};
 }
-// quat_apply / quat_apply_inverse (math.py:629-670)
-__device__ __forceinline__ V3 qapply(Q4 q, V3 v) {
-  const V3 u = {q.x, q.y, q.z};
-  const V3 t = cross(u, v) * 2.f;
-  return v + t * q.w + cross(u, t);
-}
-__device__ __forceinline__ V3 qapply_inv(Q4 q, V3 v) {
-  const V3 u = {q.x, q.y, q.z};
-  const V3 t = cross(u, v) * 2.f;
-  return v - t * q.w + cross(u, t);
-}
 // quat_error_magnitude: |axis_angle(q1 * conj(q2))| (math.py:478-506, 688-699)
 __device__ __forceinline__ float qerr(Q4 a, Q4 b) {
-  Q4 q = qmul(a, qconj(b));
+  Q4 q = qmul_torch(a, qconj(b));
   if (q.w < 0.f) q = {-q.w, -q.x, -q.y, -q.z};
   const float mag = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
   const float half = atan2f(mag, q.w), ang = 2.f * half;
@@ -81,13 +44,6 @@ __device__ __forceinline__ Q4 yaw_only(Q4 q) {
   const float yaw = atan2f(2.f * (q.w * q.z + q.x * q.y), 1.f - 2.f * (q.y * q.y + q.z * q.z));
   return {cosf(0.5f * yaw), 0.f, 0.f, sinf(0.5f * yaw)};
 }
-// quat_from_euler_xyz (math.py:275-302)
-__device__ __forceinline__ Q4 quat_euler(float r, float p, float y) {
-  const float cy = cosf(y * 0.5f), sy = sinf(y * 0.5f), cr = cosf(r * 0.5f), sr = sinf(r * 0.5f);
-  const float cp = cosf(p * 0.5f), sp = sinf(p * 0.5f);
-  return {cy * cr * cp + sy * sr * sp, cy * sr * cp - sy * cr * sp, cy * cr * sp + sy * sr * cp,
-          sy * cr * cp - cy * sr * sp};
-}
 // first two columns of matrix_from_quat, row-major ([:, :2] of the 3x3)
 __device__ __forceinline__ void mat2col(Q4 q, float* o) {
   const float w = q.w, x = q.x, y = q.y, z = q.z;
@@ -96,25 +52,8 @@ __device__ __forceinline__ void mat2col(Q4 q, float* o) {
   o[4] = 2 * (x * z - w * y);     o[5] = 2 * (y * z + w * x);
 }
 
-// counter-based uniforms: splitmix64 of (seed, env, step, draw), as velocity_task.hip
-__device__ __forceinline__ float urand(uint64_t seed, uint32_t env, uint64_t step, uint32_t draw) {
-  uint64_t z = seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(env + 1)) ^
-               (0xBF58476D1CE4E5B9ull * (step + 1)) ^ (0x94D049BB133111EBull * (uint64_t)(draw + 1));
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ float uniform(float lo, float hi, float u) { return lo + (hi - lo) * u; }
 enum : uint32_t { D_RESET_SAMPLE = 0x1000, D_CMD_SAMPLE = 0x2000, D_PUSH = 0x4000,
                   D_NOISE = 0x5000, D_RSI = 0x6000 };
-
-__device__ __forceinline__ float wave_add(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // ----------------------------------------------------------------------------- states
 // robot body link state (entity/data.py body_link_*: velocity from cvel about the root's
@@ -149,26 +88,7 @@ __device__ __forceinline__ int64_t frame_of(const mjxTrackDesc& t, int e) {
 // ----------------------------------------------------------------------------- kernels
 // action: thread per (env, joint); target = raw * scale + offset - encoder_bias
 __global__ void k_action(const mjxTrackDesc* __restrict__ T, const float* __restrict__ a) {
-  const mjxTrackDesc& t = *T;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx == 0) *t.step_counter += 1;
-  const int nj = t.njoint;
-  if (idx >= t.nworld * nj) return;
-  const int e = idx / nj, k = idx - e * nj;
-  const size_t i = (size_t)e * nj + k;
-  const float raw = a[i];
-  t.prev_prev_action[i] = t.prev_action[i];
-  t.prev_action[i] = t.action[i];
-  t.action[i] = raw;
-  float target;
-  {
-#pragma clang fp contract(off)
-    const float scaled = raw * t.action_scale[k];
-    const float processed = scaled + t.action_offset[k];
-    target = processed - t.encoder_bias[(size_t)e * nj + t.target_of_action[k]];
-  }
-  t.joint_pos_target[(size_t)e * nj + t.target_of_action[k]] = target;
-  t.ctrl[(size_t)e * t.nu + t.ctrl_of_action[k]] = target;
+  action_body<true>(*T, a);
 }
 
 // terminations + rewards + reset bookkeeping: wave per env, lane per command body / joint
@@ -447,7 +367,7 @@ __global__ __launch_bounds__(64 * kPostEnvs) void k_rsi(const mjxTrackDesc* __re
     r[k] = uniform(t.pose_range[k][0], t.pose_range[k][1], urand(seed, e, step, D_RSI + k));
     v[k] = uniform(t.vel_range[k][0], t.vel_range[k][1], urand(seed, e, step, D_RSI + 6 + k));
   }
-  const Q4 qr = qmul(quat_euler(r[3], r[4], r[5]), m.q);
+  const Q4 qr = qmul_torch(quat_euler(r[3], r[4], r[5]), m.q);
   float* q = t.qpos + (size_t)e * t.nq + t.free_q_adr;
   q[0] = m.p.x + r[0]; q[1] = m.p.y + r[1]; q[2] = m.p.z + r[2];
   q[3] = qr.w; q[4] = qr.x; q[5] = qr.y; q[6] = qr.z;
@@ -519,17 +439,18 @@ __global__ __launch_bounds__(64 * kPostEnvs) void k_targets(const mjxTrackDesc* 
   const int nmb = t.nmb;
   const Link ra = robot_link(t, e, t.anchor_body), ma = motion_link(t, e, ts, t.anchor_motion);
   const V3 dpos = {ra.p.x, ra.p.y, ma.p.z};
-  const Q4 dori = yaw_only(qmul(ra.q, qinv(ma.q)));
+  const Q4 dori = yaw_only(qmul_torch(ra.q, qinv(ma.q)));
   for (int k = lane; k < nmb; k += 64) {
     const Link m = motion_link(t, e, ts, k);
     const size_t i = (size_t)e * nmb + k;
-    const Q4 q = qmul(dori, m.q);
+    const Q4 q = qmul_torch(dori, m.q);
     const V3 p = dpos + qapply(dori, m.p - ma.p);
     float* op = t.body_pos_rel + 3 * i;
     float* oq = t.body_quat_rel + 4 * i;
     op[0] = p.x; op[1] = p.y; op[2] = p.z;
     oq[0] = q.w; oq[1] = q.x; oq[2] = q.y; oq[3] = q.z;
   }
+  // (not shared with velocity_task.hip's push: that one rotates with its qrot form)
   if (lane == 0 && t.has_push) {
     float pt = t.push_time_left[e] - t.step_dt;
     if (pt < 1e-6f) {
@@ -584,7 +505,7 @@ __global__ void k_obs(const mjxTrackDesc* __restrict__ T) {
       if (t.policy_anchor_pos) { pol = p_apos + c; noise = t.noise_anchor_pos; }
     } else {
       float m6[6];
-      mat2col(qmul(qi, ma.q), m6);
+      mat2col(qmul_torch(qi, ma.q), m6);
       const int c = i - o_aori;
       val = m6[c];
       pol = p_aori + c;
@@ -601,7 +522,7 @@ __global__ void k_obs(const mjxTrackDesc* __restrict__ T) {
     } else {
       const int k = (i - o_bori) / 6, c = (i - o_bori) % 6;
       float m6[6];
-      mat2col(qmul(qi, robot_link(t, e, t.robot_body[k]).q), m6);
+      mat2col(qmul_torch(qi, robot_link(t, e, t.robot_body[k]).q), m6);
       val = m6[c];
     }
   } else if (i < o_ang) {
@@ -625,7 +546,7 @@ __global__ void k_obs(const mjxTrackDesc* __restrict__ T) {
     pol = p_act + i - o_act; pol_val = val;
   }
   if (pol >= 0 && t.corrupt_policy && noise > 0.f)
-    pol_val += uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + pol));
+    pol_val += obs_noise(t, e, D_NOISE + pol, noise);
   if (t.obs.group[1].nterm == 0) {
     t.obs_critic[(size_t)e * nel + i] = val;
     if (pol >= 0) t.obs_policy[(size_t)e * t.npolicy + pol] = pol_val;
@@ -687,65 +608,42 @@ __global__ __launch_bounds__(128 * kLogChunks) void k_log(const mjxTrackDesc* __
 // ----------------------------------------------------------------------------- C ABI
 struct mjxTrack_ {
   mjxTrackDesc host;
-  mjxTrackDesc* dev = nullptr;
-  float* part = nullptr;  // [nblock][kAccN] k_post block partials
+  mjxtc::DeviceBuf<mjxTrackDesc> dev;
+  mjxtc::DeviceBuf<float> part;  // [nblock][kAccN] k_post block partials
   int nworld = 0;
 };
 
-static thread_local std::string g_track_err;
-static int track_fail(const std::string& s) {
-  g_track_err = s;
-  return -1;
-}
-static int track_launched(const char* what) {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : track_fail(std::string(what) + ": " + hipGetErrorString(e));
-}
+static thread_local mjxtc::ErrorSlot g_track_err;
+static int track_fail(const std::string& s) { return g_track_err.fail(s); }
+static int track_launched(const char* what) { return mjxtc::launched(g_track_err, what); }
 
 // The tracking descriptor's indices and kinds against its declared sizes (as validate_task in
 // velocity_task.hip): a mismatch is an error code, never a device fault.
 static std::string validate_track(const mjxTrackDesc& t) {
-  auto in = [](int v, int n) { return v >= 0 && v < n; };
-  auto span = [](int adr, int len, int n) { return adr >= 0 && adr + len <= n; };
-  char buf[256];
-  auto err = [&](const char* fmt, int a, int b) {
-    snprintf(buf, sizeof buf, fmt, a, b);
-    return std::string(buf);
-  };
-  if (t.nworld <= 0 || t.nq <= 0 || t.nv <= 0 || t.nu <= 0 || t.nbody <= 0 || t.nsensordata < 0)
-    return "non-positive model or batch size";
-  if (t.njoint < 1) return "no joints";
-  const void* need[] = {t.qpos, t.qvel, t.ctrl, t.xpos, t.xquat, t.cvel, t.subtree_com, t.sensordata,
-                        t.encoder_bias, t.env_origins, t.m_joint_pos, t.m_joint_vel, t.m_body_pos,
-                        t.m_body_quat, t.m_body_lin, t.m_body_ang, t.action, t.prev_action,
-                        t.prev_prev_action, t.joint_pos_target, t.episode_length, t.time_steps,
-                        t.body_pos_rel, t.body_quat_rel, t.bin_failed_count, t.current_bin_failed,
-                        t.sampling, t.metrics, t.time_left, t.command_counter, t.episode_sums,
-                        t.step_reward, t.reward_buf, t.reset_buf, t.terminated, t.time_outs,
-                        t.term_dones, t.resample_mask, t.obs_policy, t.obs_critic, t.log_reward,
-                        t.log_termination, t.log_metric, t.step_counter};
-  for (size_t i = 0; i < sizeof need / sizeof need[0]; i++)
-    if (!need[i]) return err("required buffer %d of the descriptor is null", (int)i, 0);
-  if (t.has_push && !t.push_time_left) return "has_push without push_time_left";
-  if (!in(t.root_body, t.nbody)) return err("root_body %d outside [0, %d)", t.root_body, t.nbody);
-  if (!span(t.free_q_adr, 7, t.nq)) return err("free joint qpos %d + 7 past nq %d", t.free_q_adr, t.nq);
-  if (!span(t.free_v_adr, 6, t.nv)) return err("free joint qvel %d + 6 past nv %d", t.free_v_adr, t.nv);
-  for (int j = 0; j < t.njoint; j++) {
-    if (!in(t.joint_q_adr[j], t.nq)) return err("joint %d qpos address outside [0, nq=%d)", j, t.nq);
-    if (!in(t.joint_v_adr[j], t.nv)) return err("joint %d qvel address outside [0, nv=%d)", j, t.nv);
-    if (!in(t.ctrl_of_action[j], t.nu)) return err("action %d ctrl index outside [0, nu=%d)", j, t.nu);
-    if (!in(t.target_of_action[j], t.njoint))
-      return err("action %d target column outside [0, njoint=%d)", j, t.njoint);
+  using mjxtc::in;
+  const auto err = mjxtc::errf;
+  {
+    const std::string why = mjxtc::check_common(t);
+    if (!why.empty()) return why;
   }
+  const void* const need[] = {t.qpos, t.qvel, t.ctrl, t.xpos, t.xquat, t.cvel, t.subtree_com, t.sensordata,
+                              t.encoder_bias, t.env_origins, t.m_joint_pos, t.m_joint_vel, t.m_body_pos,
+                              t.m_body_quat, t.m_body_lin, t.m_body_ang, t.action, t.prev_action,
+                              t.prev_prev_action, t.joint_pos_target, t.episode_length, t.time_steps,
+                              t.body_pos_rel, t.body_quat_rel, t.bin_failed_count, t.current_bin_failed,
+                              t.sampling, t.metrics, t.time_left, t.command_counter, t.episode_sums,
+                              t.step_reward, t.reward_buf, t.reset_buf, t.terminated, t.time_outs,
+                              t.term_dones, t.resample_mask, t.obs_policy, t.obs_critic, t.log_reward,
+                              t.log_termination, t.log_metric, t.step_counter};
+  {
+    const std::string why = mjxtc::check_buffers(need);
+    if (!why.empty()) return why;
+  }
+  if (t.has_push && !t.push_time_left) return "has_push without push_time_left";
   for (int k = 0; k < t.nmb; k++)
     if (!in(t.robot_body[k], t.nbody)) return err("command body %d: model body outside [0, %d)", k, t.nbody);
   if (!in(t.anchor_motion, t.nmb)) return err("anchor_motion %d outside [0, nmb=%d)", t.anchor_motion, t.nmb);
   if (!in(t.anchor_body, t.nbody)) return err("anchor_body %d outside [0, %d)", t.anchor_body, t.nbody);
-  if (!span(t.imu_lin_vel_adr, 3, t.nsensordata) || !span(t.imu_ang_vel_adr, 3, t.nsensordata))
-    return err("imu velocity sensors (%d, %d) + 3 past nsensordata", t.imu_lin_vel_adr, t.imu_ang_vel_adr);
-  if (t.selfcol_found_adr >= t.nsensordata)
-    return err("self-collision sensor %d outside [-1, %d)", t.selfcol_found_adr, t.nsensordata);
-  if (t.max_episode_length <= 0 || !(t.step_dt > 0.f)) return "non-positive episode length or step_dt";
   if (t.sampling_mode < 0 || t.sampling_mode > 2) return err("unknown sampling_mode %d", t.sampling_mode, 0);
   const uint32_t body_bits = t.nmb >= 32 ? 0xffffffffu : (1u << t.nmb) - 1u;
   for (int k = 0; k < t.nreward; k++) {
@@ -783,36 +681,26 @@ int mjx_track_create(const mjxTrackDesc* d, mjxTrack** out) {
     const std::string why = validate_track(*d);
     if (!why.empty()) return track_fail("mjx_track_create: " + why);
   }
-  auto* t = new mjxTrack_();
+  // every early return below frees what the handle owns so far (DeviceBuf members)
+  auto t = std::make_unique<mjxTrack_>();
   t->host = *d;
   {
     // segment tables against the layout's frames; fills their derived offsets
     const int width[2] = {d->npolicy, d->ncritic};
     const std::string why = mjxobs::prepare(t->host.obs, frame, width);
-    if (!why.empty()) {
-      delete t;
-      return track_fail("mjx_track_create: " + why);
-    }
+    if (!why.empty()) return track_fail("mjx_track_create: " + why);
   }
   t->nworld = d->nworld;
-  if (hipMalloc((void**)&t->dev, sizeof(mjxTrackDesc)) != hipSuccess ||
-      hipMalloc((void**)&t->part, sizeof(float) * mjtr::kAccN *
-                ((t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs + 1)) != hipSuccess) {
-    delete t;
+  if (!t->dev.alloc(1) ||
+      !t->part.alloc((size_t)mjtr::kAccN * ((t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs + 1)))
     return track_fail("hipMalloc failed");
-  }
-  if (hipMemcpy(t->dev, &t->host, sizeof(mjxTrackDesc), hipMemcpyHostToDevice) != hipSuccess) {
-    delete t;
+  if (hipMemcpy(t->dev.get(), &t->host, sizeof(mjxTrackDesc), hipMemcpyHostToDevice) != hipSuccess)
     return track_fail("upload failed");
-  }
-  *out = t;
+  *out = t.release();
   return 0;
 }
 
 int mjx_track_destroy(mjxTrack* t) {
-  if (!t) return 0;
-  if (t->dev) (void)hipFree(t->dev);
-  if (t->part) (void)hipFree(t->part);
   delete t;
   return 0;
 }
@@ -821,15 +709,15 @@ int mjx_track_action(mjxTrack* t, const float* action, void* stream) {
   if (!t) return track_fail("null task");
   const long n = (long)t->nworld * t->host.njoint;
   hipLaunchKernelGGL(mjtr::k_action, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, t->dev, action);
+                     (hipStream_t)stream, t->dev.get(), action);
   return track_launched("k_action");
 }
 
 int mjx_track_post(mjxTrack* t, void* stream) {
   if (!t) return track_fail("null task");
   hipLaunchKernelGGL(mjtr::k_post, dim3((t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs),
-                     dim3(64 * mjtr::kPostEnvs), 0, (hipStream_t)stream, t->dev, t->part);
-  hipLaunchKernelGGL(mjtr::k_log, dim3(1), dim3(128 * mjtr::kLogChunks), 0, (hipStream_t)stream, t->dev, t->part,
+                     dim3(64 * mjtr::kPostEnvs), 0, (hipStream_t)stream, t->dev.get(), t->part.get());
+  hipLaunchKernelGGL(mjtr::k_log, dim3(1), dim3(128 * mjtr::kLogChunks), 0, (hipStream_t)stream, t->dev.get(), t->part.get(),
                      (t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs);
   return track_launched("k_post");
 }
@@ -838,9 +726,9 @@ int mjx_track_reset(mjxTrack* t, void* stream) {
   if (!t) return track_fail("null task");
   const int nwave = (t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs;  // blocks of kPostEnvs waves
   hipLaunchKernelGGL(mjtr::k_bins, dim3(1), dim3(mjtr::kBinThreads), 0, (hipStream_t)stream,
-                     t->dev, (const uint8_t*)t->host.reset_buf, 0);
+                     t->dev.get(), (const uint8_t*)t->host.reset_buf, 0);
   hipLaunchKernelGGL(mjtr::k_rsi, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, (hipStream_t)stream,
-                     t->dev, (const uint8_t*)t->host.reset_buf, 1, (uint32_t)mjtr::D_RESET_SAMPLE);
+                     t->dev.get(), (const uint8_t*)t->host.reset_buf, 1, (uint32_t)mjtr::D_RESET_SAMPLE);
   return track_launched("k_rsi");
 }
 
@@ -848,20 +736,20 @@ int mjx_track_observe(mjxTrack* t, void* stream) {
   if (!t) return track_fail("null task");
   const int nwave = (t->nworld + mjtr::kPostEnvs - 1) / mjtr::kPostEnvs;  // blocks of kPostEnvs waves
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(mjtr::k_cmd, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev);
-  hipLaunchKernelGGL(mjtr::k_bins, dim3(1), dim3(mjtr::kBinThreads), 0, s, t->dev,
+  hipLaunchKernelGGL(mjtr::k_cmd, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev.get());
+  hipLaunchKernelGGL(mjtr::k_bins, dim3(1), dim3(mjtr::kBinThreads), 0, s, t->dev.get(),
                      (const uint8_t*)t->host.resample_mask, 1);
-  hipLaunchKernelGGL(mjtr::k_rsi, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev,
+  hipLaunchKernelGGL(mjtr::k_rsi, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev.get(),
                      (const uint8_t*)t->host.resample_mask, 0, (uint32_t)mjtr::D_CMD_SAMPLE);
-  hipLaunchKernelGGL(mjtr::k_targets, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev);
+  hipLaunchKernelGGL(mjtr::k_targets, dim3(nwave), dim3(64 * mjtr::kPostEnvs), 0, s, t->dev.get());
   const bool hist = mjxobs::enabled(t->host.obs);
   const long n = (long)t->nworld * (hist ? t->host.obs.group[1].frame : t->host.ncritic);
-  hipLaunchKernelGGL(mjtr::k_obs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->dev);
+  hipLaunchKernelGGL(mjtr::k_obs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->dev.get());
   if (hist)
-    hipLaunchKernelGGL(mjtr::k_obs_done, dim3((unsigned)((t->nworld + 255) / 256)), dim3(256), 0, s, t->dev);
+    hipLaunchKernelGGL(mjtr::k_obs_done, dim3((unsigned)((t->nworld + 255) / 256)), dim3(256), 0, s, t->dev.get());
   return track_launched("k_obs");
 }
 
-const char* mjx_track_last_error(void) { return g_track_err.c_str(); }
+const char* mjx_track_last_error(void) { return g_track_err.msg.c_str(); }
 
 }  // extern "C"

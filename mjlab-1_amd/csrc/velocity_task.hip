@@ -6,18 +6,15 @@
 // a few hundred flops per env against ~1-2 KB of per-env state, so the kernels are
 // latency-bound; they read the mjx355 data arena and write the managers' torch tensors
 // in place.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
-#include <string>
+#include <memory>
 
-#include "../../include/mjx355_task.h"
 #include "obs_hist.h"
+#include "task_common.h"
 
 namespace mjxt {
+using namespace mjxtc;
 
 constexpr int kBlock = 128;
 
@@ -30,13 +27,9 @@ struct Acc {  // device accumulators, reduced across envs with atomics
   float count;
 };
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-// quaternions (w, x, y, z): utils/lab_api/math.py quat_apply(_inverse) :629-670
+// quat_apply (sgn 1) / quat_apply_inverse (sgn -1) of math.py:629-670 with the sign folded into
+// the quaternion's vector part.  Not mjxtc::qapply / qapply_inv: the compiler contracts the two
+// forms into different instruction sequences, and the velocity kernels keep theirs.
 __device__ __forceinline__ V3 qrot(const float* q, V3 v, float sgn) {
   const float w = q[0];
   V3 u = {sgn * q[1], sgn * q[2], sgn * q[3]};
@@ -45,41 +38,14 @@ __device__ __forceinline__ V3 qrot(const float* q, V3 v, float sgn) {
   V3 c = cross(u, t);
   return {v.x + w * t.x + c.x, v.y + w * t.y + c.y, v.z + w * t.z + c.z};
 }
-__device__ __forceinline__ V3 qapply(const float* q, V3 v) { return qrot(q, v, 1.f); }
-__device__ __forceinline__ V3 qapply_inv(const float* q, V3 v) { return qrot(q, v, -1.f); }
-__device__ __forceinline__ void qmul(const float* a, const float* b, float* r) {
-  r[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  r[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  r[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  r[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-}
-// quat_from_euler_xyz (math.py:275-302)
-__device__ __forceinline__ void quat_euler(float r, float p, float y, float* q) {
-  float cy = cosf(y * 0.5f), sy = sinf(y * 0.5f), cr = cosf(r * 0.5f), sr = sinf(r * 0.5f);
-  float cp = cosf(p * 0.5f), sp = sinf(p * 0.5f);
-  q[0] = cy * cr * cp + sy * sr * sp;
-  q[1] = cy * sr * cp - sy * cr * sp;
-  q[2] = cy * cr * sp + sy * sr * cp;
-  q[3] = sy * cr * cp - cy * sr * sp;
-}
+__device__ __forceinline__ V3 qrot_apply(const float* q, V3 v) { return qrot(q, v, 1.f); }
+__device__ __forceinline__ V3 qrot_apply_inv(const float* q, V3 v) { return qrot(q, v, -1.f); }
 __device__ __forceinline__ float wrap_to_pi(float a) {
   const float tp = 6.283185307179586f;
   float w = fmodf(a + 3.141592653589793f, tp);
   if (w < 0.f) w += tp;
   return w - 3.141592653589793f;
 }
-
-// counter-based uniform randoms: splitmix64 of (seed, env, step, draw)
-__device__ __forceinline__ float urand(uint64_t seed, uint32_t env, uint64_t step, uint32_t draw) {
-  uint64_t z = seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(env + 1)) ^
-               (0xBF58476D1CE4E5B9ull * (step + 1)) ^ (0x94D049BB133111EBull * (uint64_t)(draw + 1));
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);  // [0, 1)
-}
-__device__ __forceinline__ float uniform(float lo, float hi, float u) { return lo + (hi - lo) * u; }
 
 // draw ids (per env, per env-step), kept disjoint between kernels
 enum : uint32_t { D_RESET = 0x1000, D_CMD_RESET = 0x2000, D_CMD = 0x3000, D_PUSH = 0x4000,
@@ -96,14 +62,14 @@ __device__ __forceinline__ Root root_state(const mjxTaskDesc& t, int e) {
   const size_t nb = (size_t)t.nbody;
   const float* cv = t.cvel + ((size_t)e * nb + b) * 6;
   V3 ang = v3(cv), linc = v3(cv + 3);
-  V3 off = sub(v3(t.subtree_com + ((size_t)e * nb + b) * 3), v3(t.xpos + ((size_t)e * nb + b) * 3));
+  V3 off = v3(t.subtree_com + ((size_t)e * nb + b) * 3) - v3(t.xpos + ((size_t)e * nb + b) * 3);
   V3 c = cross(ang, off);
-  r.lin_w = sub(linc, c);
+  r.lin_w = linc - c;
   r.ang_w = ang;
   r.quat = t.xquat + ((size_t)e * nb + b) * 4;
-  r.lin_b = qapply_inv(r.quat, r.lin_w);
-  r.ang_b = qapply_inv(r.quat, r.ang_w);
-  r.grav_b = qapply_inv(r.quat, V3{0.f, 0.f, -1.f});
+  r.lin_b = qrot_apply_inv(r.quat, r.lin_w);
+  r.ang_b = qrot_apply_inv(r.quat, r.ang_w);
+  r.grav_b = qrot_apply_inv(r.quat, V3{0.f, 0.f, -1.f});
   return r;
 }
 // site velocity (world, linear part) with the entity root's subtree com
@@ -112,7 +78,7 @@ __device__ __forceinline__ V3 site_lin_vel(const mjxTaskDesc& t, int e, int site
   const float* cv = t.cvel + ((size_t)e * nb + body) * 6;
   V3 sc = v3(t.subtree_com + ((size_t)e * nb + t.root_body) * 3);
   V3 p = v3(t.site_xpos + ((size_t)e * t.nsite + site) * 3);
-  return sub(v3(cv + 3), cross(v3(cv), sub(sc, p)));
+  return v3(cv + 3) - cross(v3(cv), sc - p);
 }
 __device__ __forceinline__ float command_active(const float* c, float thr) {
   return (sqrtf(c[0] * c[0] + c[1] * c[1]) + fabsf(c[2])) > thr ? 1.f : 0.f;
@@ -124,32 +90,8 @@ __device__ __forceinline__ float command_gate(const mjxTaskDesc& t, const float*
 }
 
 // ----------------------------------------------------------------------------- kernels
-// Thread per (env, joint): a thread-per-env loop serialises every iteration on a global
-// load, since its stores may alias the next iteration's loads.
 __global__ void k_action(const mjxTaskDesc* __restrict__ T, const float* __restrict__ a) {
-  const mjxTaskDesc& t = *T;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx == 0) *t.step_counter += 1;  // later kernels of this env step read the new value
-  const int nj = t.njoint;
-  if (idx >= t.nworld * nj) return;
-  const int e = idx / nj, k = idx - e * nj;
-  {
-    const size_t i = (size_t)e * nj + k;
-    const float raw = a[i];
-    t.prev_prev_action[i] = t.prev_action[i];
-    t.prev_action[i] = t.action[i];
-    t.action[i] = raw;
-    // separately rounded mul + add, as torch computes raw * scale + offset (no FMA), so
-    // ctrl is bitwise identical to the torch manager path
-    float target;
-    {
-#pragma clang fp contract(off)
-      const float scaled = raw * t.action_scale[k];
-      target = scaled + t.action_offset[k];
-    }
-    t.joint_pos_target[(size_t)e * nj + t.target_of_action[k]] = target;
-    t.ctrl[(size_t)e * t.nu + t.ctrl_of_action[k]] = target;
-  }
+  action_body<false>(*T, a);
 }
 
 __global__ void k_substep(const mjxTaskDesc* __restrict__ T) {
@@ -178,11 +120,6 @@ __global__ void k_substep(const mjxTaskDesc* __restrict__ T) {
 // pose deviation under each std table, soft-limit violation, action rate.  A thread-per-env
 // loop pays two dependent global loads (joint index, then qpos) per joint.
 struct JointSums { float pose[3], lim, rate, acc2, torque2, power, jv_var; };
-__device__ __forceinline__ float wave_add(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __device__ __forceinline__ JointSums joint_sums(const mjxTaskDesc& t, int e, int lane) {
   JointSums r{{0.f, 0.f, 0.f}, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const int nj = t.njoint;
@@ -262,7 +199,7 @@ __device__ __forceinline__ void stage_env(const mjxTaskDesc& t, const int e, con
     V3 g = r.grav_b;
     float c0 = 0.f, c1 = 0.f;
     if (t.orient_body >= 0) {
-      g = qapply_inv(t.xquat + ((size_t)e * t.nbody + t.orient_body) * 4, V3{0.f, 0.f, -1.f});
+      g = qrot_apply_inv(t.xquat + ((size_t)e * t.nbody + t.orient_body) * 4, V3{0.f, 0.f, -1.f});
       const float* cv = t.cvel + ((size_t)e * t.nbody + t.orient_body) * 6;
       c0 = cv[0]; c1 = cv[1];
     }
@@ -642,11 +579,11 @@ __global__ void k_reset(const mjxTaskDesc* __restrict__ T) {
   q[0] = rs[0] + ps[0] + o[0];
   q[1] = rs[1] + ps[1] + o[1];
   q[2] = rs[2] + ps[2] + o[2];
-  float qe[4];
-  quat_euler(ps[3], ps[4], ps[5], qe);
-  qmul(rs + 3, qe, q + 3);
+  const Q4 de = quat_euler(ps[3], ps[4], ps[5]);
+  const float qe[4] = {de.w, de.x, de.y, de.z};
+  qmul_hamilton(rs + 3, qe, q + 3);
   float* v = t.qvel + (size_t)e * t.nv + t.free_v_adr;
-  V3 ang_b = qapply_inv(q + 3, V3{rs[10] + vs[3], rs[11] + vs[4], rs[12] + vs[5]});
+  V3 ang_b = qrot_apply_inv(q + 3, V3{rs[10] + vs[3], rs[11] + vs[4], rs[12] + vs[5]});
   v[0] = rs[7] + vs[0]; v[1] = rs[8] + vs[1]; v[2] = rs[9] + vs[2];
   v[3] = ang_b.x; v[4] = ang_b.y; v[5] = ang_b.z;
   // reset_joints_by_offset (events.py:123-160): clamp to soft limits
@@ -719,7 +656,7 @@ __device__ void observe_env(const mjxTaskDesc& t, int e) {
   t.cmd_time_left[e] = tl;
   if (tl <= 0.f) resample_command(t, e, step, D_CMD);
   if (t.heading_command) {
-    V3 fwd = qapply(r.quat, V3{1.f, 0.f, 0.f});
+    V3 fwd = qrot_apply(r.quat, V3{1.f, 0.f, 0.f});
     const float heading = atan2f(fwd.y, fwd.x);
     const float err = wrap_to_pi(t.heading_target[e] - heading);
     t.heading_error[e] = err;
@@ -728,6 +665,7 @@ __device__ void observe_env(const mjxTaskDesc& t, int e) {
   }
   if (t.is_standing_env[e]) c[0] = c[1] = c[2] = 0.f;
   // ---- interval event: push_by_setting_velocity (event_manager.py:124-146, events.py:209-223)
+  // (not shared with tracking_task.hip's push: that one rotates with mjxtc::qapply_inv)
   if (t.has_push) {
     float pt = t.push_time_left[e] - t.step_dt;
     if (pt < 1e-6f) {
@@ -737,7 +675,7 @@ __device__ void observe_env(const mjxTaskDesc& t, int e) {
         u[i] = uniform(t.push_vel_range[i][0], t.push_vel_range[i][1], urand(seed, e, step, D_PUSH + 1 + i));
       float* v = t.qvel + (size_t)e * t.nv + t.free_v_adr;
       const float* qq = t.qpos + (size_t)e * t.nq + t.free_q_adr + 3;
-      V3 ang_b = qapply_inv(qq, V3{r.ang_w.x + u[3], r.ang_w.y + u[4], r.ang_w.z + u[5]});
+      V3 ang_b = qrot_apply_inv(qq, V3{r.ang_w.x + u[3], r.ang_w.y + u[4], r.ang_w.z + u[5]});
       v[0] = r.lin_w.x + u[0]; v[1] = r.lin_w.y + u[1]; v[2] = r.lin_w.z + u[2];
       v[3] = ang_b.x; v[4] = ang_b.y; v[5] = ang_b.z;
     }
@@ -756,7 +694,7 @@ __device__ void observe_env(const mjxTaskDesc& t, int e) {
 // delay rings and history blocks.
 __device__ __forceinline__ void obs_put(const mjxTaskDesc& t, int e, int i, float val, bool in_policy,
                                         bool noisy, float noise) {
-  const float pv = noisy ? val + uniform(-noise, noise, urand(t.seed, e, *t.step_counter, D_NOISE + i)) : val;
+  const float pv = noisy ? val + obs_noise(t, e, D_NOISE + i, noise) : val;
   float* co = t.obs_critic + (size_t)e * t.ncritic;
   float* po = t.obs_policy + (size_t)e * t.npolicy;
   if (t.obs.group[1].nterm == 0) {
@@ -780,7 +718,7 @@ __device__ __forceinline__ void obs_jump(const mjxTaskDesc& t, int e, int i) {
     } else if (i < 6) {
       val = sd[t.imu_ang_vel_adr + i - 3]; noise = t.noise_ang_vel;
     } else if (i < 9) {
-      const V3 g = qapply_inv(t.xquat + ((size_t)e * t.nbody + t.root_body) * 4, V3{0.f, 0.f, -1.f});
+      const V3 g = qrot_apply_inv(t.xquat + ((size_t)e * t.nbody + t.root_body) * 4, V3{0.f, 0.f, -1.f});
       val = i == 6 ? g.x : i == 7 ? g.y : g.z;
       noise = t.noise_gravity;
     } else if (i < 9 + nj) {
@@ -841,7 +779,7 @@ __device__ void obs_elem(const mjxTaskDesc& t, int e, int i) {
     } else if (i < 6) {
       val = sd[t.imu_ang_vel_adr + i - 3]; noise = t.noise_ang_vel;
     } else if (i < 9) {
-      const V3 g = qapply_inv(t.xquat + ((size_t)e * t.nbody + t.root_body) * 4, V3{0.f, 0.f, -1.f});
+      const V3 g = qrot_apply_inv(t.xquat + ((size_t)e * t.nbody + t.root_body) * 4, V3{0.f, 0.f, -1.f});
       val = i == 6 ? g.x : i == 7 ? g.y : g.z;
       noise = t.noise_gravity;
     } else if (i < 9 + nj) {
@@ -988,9 +926,9 @@ __global__ __launch_bounds__(256) void k_terrain_mean(int nworld, const int64_t*
 // ----------------------------------------------------------------------------- C ABI
 struct mjxTask_ {
   mjxTaskDesc host;
-  mjxTaskDesc* dev = nullptr;
-  mjxt::Acc* acc = nullptr;
-  float* part = nullptr;  // [nblock][kAccN] k_post block partials
+  mjxtc::DeviceBuf<mjxTaskDesc> dev;
+  mjxtc::DeviceBuf<mjxt::Acc> acc;
+  mjxtc::DeviceBuf<float> part;  // [nblock][kAccN] k_post block partials
   int nworld = 0;
   // k_post's partials not yet folded into acc (k_observe_obs folds them; a second post before
   // an observe folds the first's with a k_accum launch of its own)
@@ -1000,17 +938,8 @@ struct mjxTask_ {
   int post_form = 0;
 };
 
-static thread_local std::string g_task_err;
-static int task_fail(const std::string& s) {
-  g_task_err = s;
-  return -1;
-}
-
-extern "C" {
-
-size_t mjx_task_desc_size(void) { return sizeof(mjxTaskDesc); }
-
-}  // extern "C"
+static thread_local mjxtc::ErrorSlot g_task_err;
+static int task_fail(const std::string& s) { return g_task_err.fail(s); }
 
 // Every index the kernels dereference, checked against the sizes the descriptor declares, and
 // every term / command kind against the buffers and layout it reads, before anything reaches
@@ -1018,32 +947,32 @@ size_t mjx_task_desc_size(void) { return sizeof(mjxTaskDesc); }
 // access on the GPU (round 5: a twist-command read on the jump task's [nworld, 1] command
 // faulted the device).  Returns "" when the descriptor is consistent.
 static std::string validate_task(mjxTaskDesc& t) {
-  auto in = [](int v, int n) { return v >= 0 && v < n; };
-  auto span = [](int adr, int len, int n) { return adr >= 0 && adr + len <= n; };
-  char buf[256];
-  auto err = [&](const char* fmt, int a, int b) {
-    snprintf(buf, sizeof buf, fmt, a, b);
-    return std::string(buf);
-  };
-  if (t.nworld <= 0 || t.nq <= 0 || t.nv <= 0 || t.nu <= 0 || t.nbody <= 0 || t.nsensordata < 0 ||
-      t.nsite < 0)
-    return "non-positive model or batch size";
+  using mjxtc::in;
+  using mjxtc::span;
+  const auto err = mjxtc::errf;
   if (t.njoint < 1 || t.njoint > MJX_TASK_MAX_JOINTS || t.nfeet < 0 || t.nfeet > MJX_TASK_MAX_FEET ||
       t.nreward < 0 || t.nreward > MJX_TASK_MAX_TERMS || t.ntermination < 0 ||
       t.ntermination > MJX_TASK_MAX_TERMS || t.nillegal < 0 || t.nillegal > MJX_TASK_MAX_CONTACT_SLOTS)
     return "task descriptor exceeds compiled capacities";
+  if (t.nsite < 0) return "non-positive model or batch size";
+  {
+    const std::string why = mjxtc::check_common(t);
+    if (!why.empty()) return why;
+  }
   if (t.command_kind != MJX_CMD_TWIST && t.command_kind != MJX_CMD_JUMP)
     return err("unknown command_kind %d (%d kinds)", t.command_kind, 2);
   // buffers every launch reads or writes
-  const void* need[] = {t.qpos, t.qvel, t.ctrl, t.time, t.xpos, t.xquat, t.cvel, t.subtree_com,
-                        t.sensordata, t.env_origins, t.action, t.prev_action, t.prev_prev_action,
-                        t.joint_pos_target, t.episode_length, t.command, t.cmd_time_left,
-                        t.command_counter, t.metric_err_xy, t.metric_err_yaw, t.episode_sums,
-                        t.step_reward, t.reward_buf, t.reset_buf, t.terminated, t.time_outs,
-                        t.term_dones, t.obs_policy, t.obs_critic, t.log_reward, t.log_termination,
-                        t.log_command, t.log_metric, t.step_counter};
-  for (size_t i = 0; i < sizeof need / sizeof need[0]; i++)
-    if (!need[i]) return err("required buffer %d of the descriptor is null", (int)i, 0);
+  const void* const need[] = {t.qpos, t.qvel, t.ctrl, t.time, t.xpos, t.xquat, t.cvel, t.subtree_com,
+                              t.sensordata, t.env_origins, t.action, t.prev_action, t.prev_prev_action,
+                              t.joint_pos_target, t.episode_length, t.command, t.cmd_time_left,
+                              t.command_counter, t.metric_err_xy, t.metric_err_yaw, t.episode_sums,
+                              t.step_reward, t.reward_buf, t.reset_buf, t.terminated, t.time_outs,
+                              t.term_dones, t.obs_policy, t.obs_critic, t.log_reward, t.log_termination,
+                              t.log_command, t.log_metric, t.step_counter};
+  {
+    const std::string why = mjxtc::check_buffers(need);
+    if (!why.empty()) return why;
+  }
   if (t.nfeet > 0 && (!t.site_xpos || !t.cur_air || !t.last_air || !t.cur_contact ||
                       !t.last_contact || !t.last_time || !t.peak_heights))
     return "feet declared but a foot buffer (site_xpos, air / contact times, peak heights) is null";
@@ -1053,18 +982,8 @@ static std::string validate_task(mjxTaskDesc& t) {
   if (t.command_kind == MJX_CMD_TWIST && t.heading_command &&
       (!t.heading_target || !t.heading_error || !t.is_heading_env))
     return "heading_command without its heading buffers";
-  // entity indexing
-  if (!in(t.root_body, t.nbody)) return err("root_body %d outside [0, %d)", t.root_body, t.nbody);
+  // entity indexing past the common prefix
   if (t.orient_body >= t.nbody) return err("orient_body %d outside [-1, %d)", t.orient_body, t.nbody);
-  if (!span(t.free_q_adr, 7, t.nq)) return err("free joint qpos %d + 7 past nq %d", t.free_q_adr, t.nq);
-  if (!span(t.free_v_adr, 6, t.nv)) return err("free joint qvel %d + 6 past nv %d", t.free_v_adr, t.nv);
-  for (int j = 0; j < t.njoint; j++) {
-    if (!in(t.joint_q_adr[j], t.nq)) return err("joint %d qpos address outside [0, nq=%d)", j, t.nq);
-    if (!in(t.joint_v_adr[j], t.nv)) return err("joint %d qvel address outside [0, nv=%d)", j, t.nv);
-    if (!in(t.ctrl_of_action[j], t.nu)) return err("action %d ctrl index outside [0, nu=%d)", j, t.nu);
-    if (!in(t.target_of_action[j], t.njoint))
-      return err("action %d joint_pos_target column outside [0, njoint=%d)", j, t.njoint);
-  }
   for (int s = 0; s < t.nfeet; s++) {
     if (!in(t.foot_site[s], t.nsite)) return err("foot %d site outside [0, nsite=%d)", s, t.nsite);
     if (!in(t.foot_site_body[s], t.nbody)) return err("foot %d body outside [0, nbody=%d)", s, t.nbody);
@@ -1076,13 +995,8 @@ static std::string validate_task(mjxTaskDesc& t) {
   for (int k = 0; k < t.nillegal; k++)
     if (!in(t.illegal_found_adr[k], t.nsensordata))
       return err("illegal-contact slot %d outside [0, nsensordata=%d)", k, t.nsensordata);
-  if (!span(t.imu_lin_vel_adr, 3, t.nsensordata) || !span(t.imu_ang_vel_adr, 3, t.nsensordata))
-    return err("imu velocity sensors (%d, %d) + 3 past nsensordata", t.imu_lin_vel_adr, t.imu_ang_vel_adr);
   if (t.angmom_adr >= 0 && !span(t.angmom_adr, 3, t.nsensordata))
     return err("angular-momentum sensor %d + 3 past nsensordata %d", t.angmom_adr, t.nsensordata);
-  if (t.selfcol_found_adr >= t.nsensordata)
-    return err("self-collision sensor %d outside [-1, %d)", t.selfcol_found_adr, t.nsensordata);
-  if (t.max_episode_length <= 0 || !(t.step_dt > 0.f)) return "non-positive episode length or step_dt";
   // terms: kinds, and what each reads
   for (int k = 0; k < t.nreward; k++) {
     const int kind = t.reward_kind[k];
@@ -1145,31 +1059,33 @@ static std::string validate_task(mjxTaskDesc& t) {
   return mjxobs::prepare(t.obs, frame, width);
 }
 
+using mjxtc::launched;
+
+// a kernel of one thread per env, kBlock envs per block
+static int launch_per_env(mjxTask* t, void (*kern)(const mjxTaskDesc*), const char* what, void* stream) {
+  if (!t) return task_fail("null task");
+  const int nb = (t->nworld + mjxt::kBlock - 1) / mjxt::kBlock;
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(mjxt::kBlock), 0, (hipStream_t)stream, t->dev.get());
+  return launched(g_task_err, what);
+}
+
 extern "C" {
+
+size_t mjx_task_desc_size(void) { return sizeof(mjxTaskDesc); }
 
 int mjx_task_create(const mjxTaskDesc* desc, mjxTask** out) {
   if (!desc || !out) return task_fail("null argument");
-  if (desc->njoint > MJX_TASK_MAX_JOINTS || desc->nfeet > MJX_TASK_MAX_FEET ||
-      desc->nreward > MJX_TASK_MAX_TERMS || desc->ntermination > MJX_TASK_MAX_TERMS ||
-      desc->nillegal > MJX_TASK_MAX_CONTACT_SLOTS)
-    return task_fail("task descriptor exceeds compiled capacities");
-  auto* t = new mjxTask_();
+  // every early return below frees what the handle owns so far (DeviceBuf members)
+  auto t = std::make_unique<mjxTask_>();
   t->host = *desc;
   {
-    const std::string why = validate_task(t->host);
-    if (!why.empty()) {
-      delete t;
-      return task_fail("mjx_task_create: " + why);
-    }
+    const std::string why = validate_task(t->host);  // before the first HIP call
+    if (!why.empty()) return task_fail("mjx_task_create: " + why);
   }
   t->nworld = desc->nworld;
   const size_t nblock = ((size_t)t->nworld + mjxt::kPostEnvs - 1) / mjxt::kPostEnvs;
-  if (hipMalloc((void**)&t->dev, sizeof(mjxTaskDesc)) != hipSuccess ||
-      hipMalloc((void**)&t->acc, sizeof(mjxt::Acc)) != hipSuccess ||
-      hipMalloc((void**)&t->part, sizeof(float) * mjxt::kAccN * (nblock > 0 ? nblock : 1)) != hipSuccess) {
-    delete t;
+  if (!t->dev.alloc(1) || !t->acc.alloc(1) || !t->part.alloc(mjxt::kAccN * (nblock > 0 ? nblock : 1)))
     return task_fail("hipMalloc failed");
-  }
   {
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1178,66 +1094,46 @@ int mjx_task_create(const mjxTaskDesc* desc, mjxTask** out) {
   }
   if (const char* form = getenv("MJX355_TASK_POST_FORM")) {
     const int v = atoi(form);
-    if (v != 0 && v != 1 && v != 8) {
-      mjx_task_destroy(t);
+    if (v != 0 && v != 1 && v != 8)
       return task_fail("mjx_task_create: MJX355_TASK_POST_FORM must be 0, 1 or 8");
-    }
     t->post_form = v;
   }
-  if (hipMemcpy(t->dev, &t->host, sizeof(mjxTaskDesc), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(t->acc, 0, sizeof(mjxt::Acc)) != hipSuccess) {
-    delete t;
+  if (hipMemcpy(t->dev.get(), &t->host, sizeof(mjxTaskDesc), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(t->acc.get(), 0, sizeof(mjxt::Acc)) != hipSuccess)
     return task_fail("upload failed");
-  }
-  *out = t;
+  *out = t.release();
   return 0;
 }
 
 int mjx_task_destroy(mjxTask* t) {
-  if (!t) return 0;
-  if (t->dev) (void)hipFree(t->dev);
-  if (t->acc) (void)hipFree(t->acc);
-  if (t->part) (void)hipFree(t->part);
   delete t;
   return 0;
 }
 
-#define TASK_LAUNCH(kern, ...)                                                             \
-  do {                                                                                     \
-    if (!t) return task_fail("null task");                                                 \
-    const int nb = (t->nworld + mjxt::kBlock - 1) / mjxt::kBlock;                          \
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(mjxt::kBlock), 0, (hipStream_t)stream, __VA_ARGS__); \
-    hipError_t e_ = hipGetLastError();                                                      \
-    if (e_ != hipSuccess) return task_fail(std::string(#kern ": ") + hipGetErrorString(e_)); \
-    return 0;                                                                              \
-  } while (0)
-
 int mjx_task_action(mjxTask* t, const float* action, void* stream) {
   if (!t) return task_fail("null task");
-  const long n = (long)t->nworld * t->host.njoint;
-  hipLaunchKernelGGL(mjxt::k_action, dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)),
-                     dim3(256), 0, (hipStream_t)stream, t->dev, action);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : task_fail(std::string("k_action: ") + hipGetErrorString(e));
+  const long n = (long)t->nworld * t->host.njoint;  // > 0: checked at create
+  hipLaunchKernelGGL(mjxt::k_action, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, t->dev.get(), action);
+  return launched(g_task_err, "k_action");
 }
-int mjx_task_substep(mjxTask* t, void* stream) { TASK_LAUNCH(mjxt::k_substep, t->dev); }
+int mjx_task_substep(mjxTask* t, void* stream) { return launch_per_env(t, mjxt::k_substep, "k_substep", stream); }
 int mjx_task_post(mjxTask* t, void* stream) {
   if (!t) return task_fail("null task");
   const int nblock = (t->nworld + mjxt::kPostEnvs - 1) / mjxt::kPostEnvs;
   if (t->pending_nblock > 0)  // a post without an observe since: fold its partials first
     hipLaunchKernelGGL(mjxt::k_accum, dim3(1), dim3(128 * mjxt::kAccChunks), 0, (hipStream_t)stream,
-                       t->part, t->pending_nblock, t->acc);
+                       t->part.get(), t->pending_nblock, t->acc.get());
   if (t->post_form ? t->post_form == 8 : nblock > t->ncu)
     hipLaunchKernelGGL(mjxt::k_post<8>, dim3(nblock), dim3(64 * mjxt::kPostEnvs), 0, (hipStream_t)stream,
-                       t->dev, t->part);
+                       t->dev.get(), t->part.get());
   else
     hipLaunchKernelGGL(mjxt::k_post<1>, dim3(nblock), dim3(64 * mjxt::kPostEnvs), 0, (hipStream_t)stream,
-                       t->dev, t->part);
+                       t->dev.get(), t->part.get());
   t->pending_nblock = nblock;  // folded by the next mjx_task_observe (k_observe_obs block 0)
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : task_fail(std::string("k_post: ") + hipGetErrorString(e));
+  return launched(g_task_err, "k_post");
 }
-int mjx_task_reset(mjxTask* t, void* stream) { TASK_LAUNCH(mjxt::k_reset, t->dev); }
+int mjx_task_reset(mjxTask* t, void* stream) { return launch_per_env(t, mjxt::k_reset, "k_reset", stream); }
 int mjx_task_observe(mjxTask* t, void* stream) {
   if (!t) return task_fail("null task");
   const int nj = t->host.njoint, nf = t->host.nfeet;
@@ -1255,14 +1151,13 @@ int mjx_task_observe(mjxTask* t, void* stream) {
   }
   (void)nel;
   hipLaunchKernelGGL(mjxt::k_observe_obs, dim3((t->nworld + mjxt::kObsEnvs - 1) / mjxt::kObsEnvs),
-                     dim3(64 * mjxt::kObsEnvs), 0, (hipStream_t)stream, t->dev, t->acc, t->part,
-                     t->pending_nblock);
+                     dim3(64 * mjxt::kObsEnvs), 0, (hipStream_t)stream, t->dev.get(), t->acc.get(),
+                     t->part.get(), t->pending_nblock);
   t->pending_nblock = 0;
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : task_fail(std::string("k_observe: ") + hipGetErrorString(e));
+  return launched(g_task_err, "k_observe");
 }
 
-const char* mjx_task_last_error(void) { return g_task_err.c_str(); }
+const char* mjx_task_last_error(void) { return g_task_err.msg.c_str(); }
 
 int mjx_terrain_levels(int nworld, const uint8_t* mask, const float* xpos, int nbody, int root_body,
                        const float* command, float half_patch, float episode_length_s,
@@ -1278,8 +1173,7 @@ int mjx_terrain_levels(int nworld, const uint8_t* mask, const float* xpos, int n
                      types, levels, terrain_origins, nrows, ncols, env_origins, seed, counter);
   hipLaunchKernelGGL(mjxt::k_terrain_mean, dim3(1), dim3(256), 0, (hipStream_t)stream, nworld,
                      levels, mean_level, counter);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : task_fail(std::string("k_terrain: ") + hipGetErrorString(e));
+  return launched(g_task_err, "k_terrain");
 }
 
 }  // extern "C"

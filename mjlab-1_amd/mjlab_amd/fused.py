@@ -17,6 +17,13 @@ that are exposed in `extras["log"]` under the reference's key names.
 Observation history and the per-env redrawn delay run in the observe kernels
 (`FusedObsHistory`, the descriptors' `obs` tail); the observation rows are the history
 storage, seeded from and handed back to the manager's buffers.
+
+Structure: `FusedStepBase` is what this module's `FusedVelocityStep` / `FusedJumpStep` and
+`fused_tracking.FusedTrackingStep` share: the ctypes binding of one entry-point family from a
+per-class table, the device handle (`upload`, `release`, the finaliser), the `step` skeleton
+with its `_substeps` and `_before_reset` hooks, and the fillers of the descriptor fields both
+families name alike (`_sim`, `_joints`, `_termination_buffers`, `_reward_buffers`, `_push`,
+`_io`).  Term kinds and capacities are the `MJX_*` constants below, named as in the header.
 """
 
 from __future__ import annotations
@@ -30,7 +37,24 @@ import torch
 from . import jump, mdp
 from ._lib import MjxError, check, lib
 
-MAXJ, MAXF, MAXT, MAXC = 64, 8, 24, 32
+# include/mjx355_task.h by name: capacities, term / metric / command kinds
+# (tests/test_task_constants.py holds every MJX_* here against the header)
+MJX_TASK_MAX_JOINTS, MJX_TASK_MAX_FEET, MJX_TASK_MAX_TERMS, MJX_TASK_MAX_CONTACT_SLOTS = 64, 8, 24, 32
+MJX_TASK_MAX_OBS_TERMS, MJX_TASK_MAX_HISTORY, MJX_TASK_MAX_LAG = 16, 32, 15
+(MJX_RW_TRACK_LIN, MJX_RW_TRACK_ANG, MJX_RW_FLAT_ORIENT, MJX_RW_POSE, MJX_RW_BODY_ANG_VEL,
+ MJX_RW_ANGMOM, MJX_RW_JOINT_POS_LIMITS, MJX_RW_ACTION_RATE, MJX_RW_FEET_AIR_TIME,
+ MJX_RW_FEET_CLEARANCE, MJX_RW_FEET_SWING, MJX_RW_FEET_SLIP, MJX_RW_SOFT_LANDING,
+ MJX_RW_SELF_COLLISION, MJX_RW_JUMP_HEIGHT, MJX_RW_EXPLOSIVE_TAKEOFF, MJX_RW_SYNC_EXTENSION,
+ MJX_RW_VERTICAL_IMPULSE, MJX_RW_AIR_TIME_BONUS, MJX_RW_LANDING_BALANCE,
+ MJX_RW_SYMMETRIC_LANDING, MJX_RW_ACTION_ACC, MJX_RW_JOINT_TORQUES, MJX_RW_IS_ALIVE) = range(24)
+(MJX_TM_TIME_OUT, MJX_TM_BAD_ORIENT, MJX_TM_ILLEGAL_CONTACT, MJX_TM_ROOT_HEIGHT,
+ MJX_TM_EXCESSIVE_FORCE) = range(5)
+(MJX_MT_ANGMOM, MJX_MT_AIR_TIME, MJX_MT_PEAK_HEIGHT, MJX_MT_SLIP, MJX_MT_LANDING, MJX_MT_PEAK_JUMP,
+ MJX_MT_JUMP_HEIGHT, MJX_MT_LANDING_SUCCESS, MJX_MT_COUNT) = range(9)
+MJX_CMD_TWIST, MJX_CMD_JUMP = 0, 1
+
+MAXJ, MAXF, MAXT, MAXC = (MJX_TASK_MAX_JOINTS, MJX_TASK_MAX_FEET, MJX_TASK_MAX_TERMS,
+                          MJX_TASK_MAX_CONTACT_SLOTS)
 _f2 = ctypes.c_float * 2
 _f62 = (ctypes.c_float * 2) * 6
 _FP = ctypes.POINTER(ctypes.c_float)
@@ -38,7 +62,7 @@ _U8 = ctypes.POINTER(ctypes.c_uint8)
 _I64 = ctypes.POINTER(ctypes.c_int64)
 _U64 = ctypes.POINTER(ctypes.c_uint64)
 _I32 = ctypes.POINTER(ctypes.c_int32)
-MAX_OBS_TERMS, MAX_HISTORY, MAX_LAG = 16, 32, 15
+MAX_OBS_TERMS, MAX_HISTORY, MAX_LAG = MJX_TASK_MAX_OBS_TERMS, MJX_TASK_MAX_HISTORY, MJX_TASK_MAX_LAG
 
 
 class ObsSeg(ctypes.Structure):
@@ -121,16 +145,22 @@ class TaskDesc(ctypes.Structure):
 
 
 _REWARD_KIND = {
-  mdp.track_linear_velocity: 0, mdp.track_angular_velocity: 1, mdp.flat_orientation: 2,
-  mdp.body_angular_velocity_penalty: 4, mdp.angular_momentum_penalty: 5,
-  mdp.joint_pos_limits: 6, mdp.action_rate_l2: 7, mdp.feet_air_time: 8,
-  mdp.feet_clearance: 9, mdp.feet_slip: 11, mdp.soft_landing: 12, mdp.self_collision_cost: 13,
+  mdp.track_linear_velocity: MJX_RW_TRACK_LIN, mdp.track_angular_velocity: MJX_RW_TRACK_ANG,
+  mdp.flat_orientation: MJX_RW_FLAT_ORIENT, mdp.body_angular_velocity_penalty: MJX_RW_BODY_ANG_VEL,
+  mdp.angular_momentum_penalty: MJX_RW_ANGMOM, mdp.joint_pos_limits: MJX_RW_JOINT_POS_LIMITS,
+  mdp.action_rate_l2: MJX_RW_ACTION_RATE, mdp.feet_air_time: MJX_RW_FEET_AIR_TIME,
+  mdp.feet_clearance: MJX_RW_FEET_CLEARANCE, mdp.feet_slip: MJX_RW_FEET_SLIP,
+  mdp.soft_landing: MJX_RW_SOFT_LANDING, mdp.self_collision_cost: MJX_RW_SELF_COLLISION,
 }
 _METRIC_KEYS = ("Metrics/angular_momentum_mean", "Metrics/air_time_mean", "Metrics/peak_height_mean",
                 "Metrics/slip_velocity_mean", "Metrics/landing_force_mean",
                 "Metrics/peak_jump_height", "Metrics/jump_height", "Metrics/landing_success_rate")
-NMETRIC = len(_METRIC_KEYS)
-_METRIC_OF_KIND = {5: 0, 8: 1, 10: 2, 11: 3, 12: 4, 18: 1}
+NMETRIC = MJX_MT_COUNT
+# the metric slot a reward kind writes (the jump_height / landing_balance slots are set with
+# their stateful terms)
+_METRIC_OF_KIND = {MJX_RW_ANGMOM: MJX_MT_ANGMOM, MJX_RW_FEET_AIR_TIME: MJX_MT_AIR_TIME,
+                   MJX_RW_FEET_SWING: MJX_MT_PEAK_HEIGHT, MJX_RW_FEET_SLIP: MJX_MT_SLIP,
+                   MJX_RW_SOFT_LANDING: MJX_MT_LANDING, MJX_RW_AIR_TIME_BONUS: MJX_MT_AIR_TIME}
 _EXCESSIVE_FORCE = (jump.excessive_landing_force,)
 _POLICY = [("base_lin_vel", mdp.builtin_sensor), ("base_ang_vel", mdp.builtin_sensor),
            ("projected_gravity", mdp.projected_gravity), ("joint_pos", mdp.joint_pos_rel),
@@ -320,8 +350,15 @@ class FusedObsHistory:
     om._obs_buffer = {k: v.clone() for k, v in obs.items()}
 
 
-class FusedVelocityStep:
-  """One env step of a velocity task as fused HIP launches (see module docstring)."""
+class FusedStepBase:
+  """What the fused steps of both families share: the ctypes binding of one entry-point family,
+  the device handle, the env step's skeleton and the descriptor fillers of the fields both
+  descriptors name alike.  A subclass gives the binding table and `_make_desc`."""
+
+  PREFIX = ""      # C symbol prefix: <PREFIX>_create, _action, _post, _reset, _observe, ...
+  DESC = None      # ctypes mirror of the family's descriptor
+  STAGES = ("post", "reset", "observe")  # entry points taking (handle, stream)
+  SIM_FIELDS = ()  # mjData arrays the descriptor points at
 
   @classmethod
   def build(cls, env):
@@ -333,17 +370,7 @@ class FusedVelocityStep:
 
   def __init__(self, env):
     self.env = env
-    L = lib()
-    L.mjx_task_desc_size.restype = ctypes.c_size_t
-    _need(L.mjx_task_desc_size() == ctypes.sizeof(TaskDesc), "mjxTaskDesc layout mismatch")
-    L.mjx_task_create.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    for n in ("mjx_task_action",):
-      getattr(L, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    for n in ("mjx_task_substep", "mjx_task_post", "mjx_task_reset", "mjx_task_observe"):
-      getattr(L, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.mjx_task_destroy.argtypes = [ctypes.c_void_p]
-    L.mjx_task_last_error.restype = ctypes.c_char_p
-    self._L = L
+    self._L = self._bind()
     self._keep = []
     self._task = None
     self._desc = self._make_desc(env)
@@ -353,6 +380,272 @@ class FusedVelocityStep:
     except Exception:
       release_explicit_actuators(self)  # the env falls back in torch mode
       raise
+
+  def _bind(self):
+    L, p = lib(), self.PREFIX
+    _need(hasattr(L, p + "_desc_size"), f"library without the {p}_* kernels")
+    getattr(L, p + "_desc_size").restype = ctypes.c_size_t
+    _need(getattr(L, p + "_desc_size")() == ctypes.sizeof(self.DESC),
+          f"mjx{self.DESC.__name__} layout mismatch")
+    getattr(L, p + "_create").argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    getattr(L, p + "_action").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    for n in self.STAGES:
+      getattr(L, f"{p}_{n}").argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    getattr(L, p + "_destroy").argtypes = [ctypes.c_void_p]
+    getattr(L, p + "_last_error").restype = ctypes.c_char_p
+    return L
+
+  def _call(self, name, *args):
+    self._ok(getattr(self._L, f"{self.PREFIX}_{name}")(self._task, *args))
+
+  def _ok(self, rc):
+    if rc != 0:
+      raise MjxError(getattr(self._L, self.PREFIX + "_last_error")().decode())
+
+  def _stream(self):
+    return ctypes.c_void_p(torch.cuda.current_stream(self.env.sim._torch_device).cuda_stream)
+
+  # ------------------------------------------------------------------ descriptor fillers
+  def _sim(self, d, env):
+    """Batch and model sizes, the mjData pointers."""
+    m, sd = env.sim.mj_model, env.sim.data
+    d.nworld, d.nq, d.nv, d.nu = env.num_envs, m.nq, m.nv, m.nu
+    d.nsensordata, d.nbody = m.nsensordata, m.nbody
+    for f in self.SIM_FIELDS:
+      setattr(d, f, _ptr(getattr(sd, f)))
+
+  def _joints(self, d, env):
+    """The joint-position action and the joints it drives, the env origins.  Every per-env
+    quantity the kernels read as one row (action offset, default joint position, soft limits)
+    or assume zero (default joint velocity) is checked.  The encoder bias is the families' one
+    difference: tracking's kernels read it per env, velocity's assume none.  Returns the
+    action term's entity."""
+    am = env.action_manager
+    _need(len(am._terms) == 1, "one action term")
+    (aterm,) = am._terms.values()
+    _need(isinstance(aterm, mdp.JointPositionAction), "JointPositionAction only")
+    robot = aterm._asset
+    self._robot = robot
+    self._explicit = explicit_actuator_entities(env, robot)
+    rdata, idx = robot.data, robot.indexing
+    if hasattr(d, "encoder_bias"):
+      d.encoder_bias = _ptr(rdata.encoder_bias)
+    else:
+      _need(float(rdata.encoder_bias.abs().max()) == 0.0 if rdata.encoder_bias.numel() else True,
+            "encoder bias")
+    nj = len(idx.joint_q_adr)
+    _need(nj <= MAXJ and aterm.action_dim == nj, "action dim == actuated joints")
+    d.root_body = int(idx.root_body_id)
+    d.free_q_adr, d.free_v_adr = int(idx.free_joint_q_adr[0]), int(idx.free_joint_v_adr[0])
+    d.njoint = nj
+    jq, jv = idx.joint_q_adr.tolist(), idx.joint_v_adr.tolist()
+    for j in range(nj):
+      d.joint_q_adr[j], d.joint_v_adr[j] = jq[j], jv[j]
+    act_local = robot._act_joint_local_t.tolist()
+    ctrl_ids = idx.ctrl_ids.tolist()
+    scale, off = aterm._scale, aterm._offset
+    _need(isinstance(off, float) or bool(torch.all(off == off[:1]).item()), "per-env action offset")
+    for k, jk in enumerate(aterm._joint_ids.tolist()):
+      d.ctrl_of_action[k] = ctrl_ids[act_local.index(jk)]
+      d.target_of_action[k] = jk
+      d.action_scale[k] = scale if isinstance(scale, float) else float(scale[0, k])
+      d.action_offset[k] = off if isinstance(off, float) else float(off[0, k])
+    _need(rdata.joint_pos_target.shape[1] == nj, "joint target width")
+    _need(torch.all(rdata.default_joint_pos == rdata.default_joint_pos[:1]).item(),
+          "per-env default joint pos")
+    _need(torch.all(rdata.soft_joint_pos_limits == rdata.soft_joint_pos_limits[:1]).item(),
+          "per-env soft limits")
+    _need(torch.all(rdata.default_joint_vel == 0).item(), "nonzero default joint vel")
+    dj = rdata.default_joint_pos[0].tolist()
+    lim = rdata.soft_joint_pos_limits[0].tolist()
+    for j in range(nj):
+      d.default_joint_pos[j] = dj[j]
+      d.soft_lo[j], d.soft_hi[j] = lim[j]
+    origins = env.scene.env_origins.contiguous()
+    self._keep.append(origins)
+    d.env_origins = _ptr(origins)
+    return robot
+
+  def _termination_buffers(self, d, env):
+    """Per-term done flags as rows of one [ntermination, n] tensor, the managers' flags, the
+    reset mask."""
+    tm, n, dev = env.termination_manager, env.num_envs, torch.device(env.device)
+    self._term_dones = torch.zeros(max(d.ntermination, 1), n, dtype=torch.bool, device=dev)
+    for k, name in enumerate(tm._term_names):
+      tm._term_dones[name] = self._term_dones[k]
+    d.term_dones = _ptr(self._term_dones, _U8)
+    d.terminated = _ptr(tm._terminated_buf, _U8)
+    d.time_outs = _ptr(tm._truncated_buf, _U8)
+    self.reset_buf = torch.zeros(n, dtype=torch.bool, device=dev)
+    d.reset_buf = _ptr(self.reset_buf, _U8)
+    self._term_names = list(tm._term_names)
+
+  def _reward_buffers(self, d, env):
+    """Episode sums as rows of one [nreward, n] tensor; step reward / reward buffers; timing."""
+    rm, n, dev = env.reward_manager, env.num_envs, torch.device(env.device)
+    self._episode_sums = torch.zeros(max(d.nreward, 1), n, device=dev)
+    for k, name in enumerate(rm._term_names):
+      self._episode_sums[k].copy_(rm._episode_sums[name])
+      rm._episode_sums[name] = self._episode_sums[k]
+    d.episode_sums = _ptr(self._episode_sums)
+    d.step_reward, d.reward_buf = _ptr(rm._step_reward), _ptr(rm._reward_buf)
+    # timing
+    d.step_dt, d.episode_length_s = float(env.step_dt), float(env.max_episode_length_s)
+    # play configs use a 1e9 s episode: clamp into the descriptor's int32 (never reached)
+    d.max_episode_length = min(int(env.max_episode_length), 2 ** 31 - 1)
+    _need(env.episode_length_buf.dtype == torch.int64, "episode length dtype")
+    d.episode_length = _ptr(env.episode_length_buf, _I64)
+    self._reward_names = list(rm._term_names)
+
+  def _push(self, d, env):
+    """The optional interval event: push_by_setting_velocity on its own timer."""
+    em = env.event_manager
+    inter = em._mode_term_cfgs.get("interval", [])
+    _need(len(inter) <= 1, "one interval event")
+    if inter:
+      c = inter[0]
+      _need(c.func is mdp.push_by_setting_velocity and not c.is_global_time, "push event")
+      d.has_push = 1
+      d.push_interval[0], d.push_interval[1] = map(float, c.interval_range_s)
+      for i, (lo, hi) in enumerate(_range6(c.params["velocity_range"])):
+        d.push_vel_range[i][0], d.push_vel_range[i][1] = lo, hi
+      d.push_time_left = _ptr(em._interval_time_left[0])
+    else:
+      self._dummy_push = torch.zeros(env.num_envs, device=torch.device(env.device))
+      d.push_time_left = _ptr(self._dummy_push)
+
+  def _io(self, d, env, pol, cri, nmetric):
+    """Observation history / delay (the descriptor's segment tables and the row widths they
+    imply; the single-frame widths stay when no term asks for either), observation buffers,
+    action pointers, seed, log scalars."""
+    om, am, n, dev = env.observation_manager, env.action_manager, env.num_envs, torch.device(env.device)
+    self._obs_hist = FusedObsHistory.build(d, env, pol, cri)
+    if self._obs_hist is not None:
+      d.npolicy, d.ncritic = self._obs_hist.widths
+    _need(om.group_obs_dim["policy"] == (d.npolicy,) and om.group_obs_dim["critic"] == (d.ncritic,),
+          "observation dims")
+    self.obs = {"policy": torch.zeros(n, d.npolicy, device=dev),
+                "critic": torch.zeros(n, d.ncritic, device=dev)}
+    d.obs_policy, d.obs_critic = _ptr(self.obs["policy"]), _ptr(self.obs["critic"])
+    if self._obs_hist is not None:
+      self._obs_hist.seed(self.obs)
+    d.action, d.prev_action = _ptr(am._action), _ptr(am._prev_action)
+    d.prev_prev_action = _ptr(am._prev_prev_action)
+    d.joint_pos_target = _ptr(self._robot.data.joint_pos_target)
+    d.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    # logs
+    self.log_reward = torch.zeros(max(d.nreward, 1), device=dev)
+    self.log_term = torch.zeros(max(d.ntermination, 1), device=dev)
+    if hasattr(d, "log_command"):
+      self.log_cmd = torch.zeros(2, device=dev)
+      d.log_command = _ptr(self.log_cmd)
+    self.log_metric = torch.zeros(nmetric, device=dev)
+    self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    d.log_reward, d.log_termination = _ptr(self.log_reward), _ptr(self.log_term)
+    d.log_metric = _ptr(self.log_metric)
+    d.step_counter = _ptr(self.step_counter, _U64)
+    self._keep.extend([self._term_dones, self.reset_buf, self._episode_sums])
+
+  @staticmethod
+  def _slot_adrs(sensor, field):
+    _need(getattr(sensor, "_num_slots", 1) == 1, "one contact slot per primary")
+    return [adr for _, f, adr, _ in sensor._slots if f == field]
+
+  # ------------------------------------------------------------------ device handle
+  def _refresh_desc(self):
+    """Fields a curriculum moves besides the reward weights (hook of `upload`)."""
+
+  def upload(self):
+    """(Re)create the device copy of the descriptor (after a curriculum changed reward
+    weights or what `_refresh_desc` covers)."""
+    L, p = self._L, self.PREFIX
+    self._refresh_desc()
+    for k, c in enumerate(self.env.reward_manager._term_cfgs):
+      self._desc.reward_weight[k] = float(c.weight)
+    if self._task is not None:
+      getattr(L, p + "_destroy")(self._task)
+    h = ctypes.c_void_p()
+    self._ok(getattr(L, p + "_create")(ctypes.byref(self._desc), ctypes.byref(h)))
+    self._task = h
+
+  def release(self) -> None:
+    """Called when the env drops or replaces this fused step (enable_graph): the observation
+    history / delay state goes back to the manager's buffers, the engine-mode actuators to
+    the torch path."""
+    if getattr(self, "_obs_hist", None) is not None:
+      self._obs_hist.hand_back(self.obs)
+      self._obs_hist = None
+    release_explicit_actuators(self)
+
+  def __del__(self):
+    # no hand-back from a finaliser: it may run while the interpreter tears the manager's
+    # tensors down (enable_graph releases explicitly)
+    self._obs_hist = None
+    try:
+      self.release()
+    except Exception:
+      pass
+    try:
+      if self._task is not None:
+        getattr(self._L, self.PREFIX + "_destroy")(self._task)
+    except Exception:
+      pass
+
+  # ------------------------------------------------------------------ the env step
+  # False while the env records a graph whose replays run apply_action() before them (the
+  # action kernel then reads the caller's tensor: no copy into a static input buffer)
+  action_in_step = True
+
+  def apply_action(self, action: torch.Tensor):
+    self._call("action", ctypes.c_void_p(action.data_ptr()), self._stream())
+
+  def _substeps(self, stream):
+    """The `decimation` physics substeps: one mjx_step, whose full mjData outputs (frames,
+    contacts, forces) are written after the last substep only."""
+    self.env.sim.step(nsubstep=self.env.cfg.decimation)
+
+  def _before_reset(self):
+    """Work on this step's reset mask before the reset kernels run (hook of `step`)."""
+
+  def step(self, action: torch.Tensor):
+    env, sim = self.env, self.env.sim
+    stream = self._stream()
+    if self.action_in_step:
+      self._call("action", ctypes.c_void_p(action.data_ptr()), stream)
+    self._substeps(stream)
+    self._call("post", stream)
+    self._before_reset()
+    mask = ctypes.c_void_p(self.reset_buf.data_ptr())
+    check(lib().mjx_reset(sim._sim, mask, stream))
+    self._call("reset", stream)
+    if self._engine_act is not None:  # delay history of the reset envs: cleared, one frame
+      self._engine_act.reset_masked(self.reset_buf)
+    check(lib().mjx_forward_masked(sim._sim, mask, stream))
+    self._call("observe", stream)
+    tm = env.termination_manager
+    return self.obs, env.reward_manager._reward_buf, tm._terminated_buf, tm._truncated_buf
+
+  def log(self) -> dict:
+    """Episode logs as device scalars under the reference's keys."""
+    out = {}
+    for k, name in enumerate(self._reward_names):
+      out["Episode_Reward/" + name] = self.log_reward[k]
+    for k, name in enumerate(self._term_names):
+      out["Episode_Termination/" + name] = self.log_term[k]
+    return out
+
+
+class FusedVelocityStep(FusedStepBase):
+  """One env step of a velocity task as fused HIP launches (see module docstring)."""
+
+  PREFIX, DESC = "mjx_task", TaskDesc
+  STAGES = ("substep", "post", "reset", "observe")
+  SIM_FIELDS = ("qpos", "qvel", "ctrl", "time", "xpos", "xquat", "cvel", "subtree_com",
+                "site_xpos", "sensordata")
+  _CMD_LOG = ("Metrics/twist/error_vel_xy", "Metrics/twist/error_vel_yaw")
+
+  def __init__(self, env):
+    super().__init__(env)
     self._engine_air = self._track_air_time()
 
   # ------------------------------------------------------------------ descriptor
@@ -372,7 +665,7 @@ class FusedVelocityStep:
       f, p = c.func, c.params
       d.reward_weight[k] = float(c.weight)
       if isinstance(f, mdp.variable_posture):
-        kind = 3
+        kind = MJX_RW_POSE
         d.reward_p0[k], d.reward_p1[k] = float(p.get("walking_threshold", 0.5)), float(p.get("running_threshold", 1.5))
         for j in range(nj):
           d.std_standing[j] = float(f.std_standing[j])
@@ -380,7 +673,7 @@ class FusedVelocityStep:
           d.std_running[j] = float(f.std_running[j])
         _need(f.std_standing.numel() == nj, "posture over all joints")
       elif isinstance(f, mdp.feet_swing_height):
-        kind = 10
+        kind = MJX_RW_FEET_SWING
         d.reward_p0[k], d.reward_p1[k] = float(p["target_height"]), float(p["command_threshold"])
         feet_sensor = self._same(feet_sensor, p["sensor_name"])
         site_names = self._same(site_names, tuple(p["asset_cfg"].site_names))
@@ -388,29 +681,29 @@ class FusedVelocityStep:
       else:
         _need(f in _REWARD_KIND, f"reward term {name}")
         kind = _REWARD_KIND[f]
-        if kind in (0, 1):
+        if kind in (MJX_RW_TRACK_LIN, MJX_RW_TRACK_ANG):
           d.reward_p0[k] = float(p["std"])
           _need(p["command_name"] == "twist", "command name")
-        elif kind in (2, 4):
+        elif kind in (MJX_RW_FLAT_ORIENT, MJX_RW_BODY_ANG_VEL):
           orient_body = self._orient(d, k, kind, p, robot, orient_body)
-        elif kind == 5:
+        elif kind == MJX_RW_ANGMOM:
           d.angmom_adr = sens[p["sensor_name"]][0]
-        elif kind == 8:
+        elif kind == MJX_RW_FEET_AIR_TIME:
           d.reward_p0[k], d.reward_p1[k] = float(p["threshold_min"]), float(p["threshold_max"])
           d.reward_p2[k] = float(p["command_threshold"])
           feet_sensor = self._same(feet_sensor, p["sensor_name"])
-        elif kind == 9:
+        elif kind == MJX_RW_FEET_CLEARANCE:
           d.reward_p0[k], d.reward_p1[k] = float(p["target_height"]), float(p["command_threshold"])
           site_names = self._same(site_names, tuple(p["asset_cfg"].site_names))
-        elif kind == 11:
+        elif kind == MJX_RW_FEET_SLIP:
           d.reward_p0[k] = float(p["command_threshold"])
           feet_sensor = self._same(feet_sensor, p["sensor_name"])
           site_names = self._same(site_names, tuple(p["asset_cfg"].site_names))
-        elif kind == 12:
+        elif kind == MJX_RW_SOFT_LANDING:
           d.reward_p0[k] = float(p.get("command_threshold", 0.05))
           d.reward_p1[k] = float(p.get("command_name") is None)  # ungated
           feet_sensor = self._same(feet_sensor, p["sensor_name"])
-        elif kind == 13:
+        elif kind == MJX_RW_SELF_COLLISION:
           s = scene[p["sensor_name"]]
           d.selfcol_found_adr = self._slot_adrs(s, "found")[0]
       d.reward_kind[k] = kind
@@ -456,67 +749,18 @@ class FusedVelocityStep:
       _need(pol[i][1].noise is None, "noise on actions/command")
     d.npolicy = 9 + 3 * nj + 3
     d.ncritic = d.npolicy + (6 * d.nfeet if d.critic_extras else 0)
-    self._obs_history(d, env, pol, cri)
-    self._io(d, env)
+    self._io(d, env, pol, cri, NMETRIC)
     return d
 
   def _base(self, d, env):
     """Simulation pointers, the joint-position action, joints, default root state, origins."""
-    sim, scene, m = env.sim, env.scene, env.sim.mj_model
-    dev = torch.device(env.device)
-    sd = sim.data
-    n = env.num_envs
-    d.nworld, d.nq, d.nv, d.nu = n, m.nq, m.nv, m.nu
-    d.nsensordata, d.nbody, d.nsite = m.nsensordata, m.nbody, m.nsite
-    for f in ("qpos", "qvel", "ctrl", "time", "xpos", "xquat", "cvel", "subtree_com",
-              "site_xpos", "sensordata"):
-      setattr(d, f, _ptr(getattr(sd, f)))
-    # actions
-    am = env.action_manager
-    _need(len(am._terms) == 1, "one action term")
-    (aterm,) = am._terms.values()
-    _need(isinstance(aterm, mdp.JointPositionAction), "JointPositionAction only")
-    robot = aterm._asset
-    self._robot = robot
-    self._explicit = explicit_actuator_entities(env, robot)
-    rdata = robot.data
-    _need(float(rdata.encoder_bias.abs().max()) == 0.0 if rdata.encoder_bias.numel() else True,
-          "encoder bias")
-    idx = robot.indexing
-    nj = len(idx.joint_q_adr)
-    _need(nj <= MAXJ and aterm.action_dim == nj, "action dim == actuated joints")
-    d.root_body = int(idx.root_body_id)
-    d.free_q_adr, d.free_v_adr = int(idx.free_joint_q_adr[0]), int(idx.free_joint_v_adr[0])
-    d.njoint = nj
-    jq, jv = idx.joint_q_adr.tolist(), idx.joint_v_adr.tolist()
-    for j in range(nj):
-      d.joint_q_adr[j], d.joint_v_adr[j] = jq[j], jv[j]
-    jids = aterm._joint_ids.tolist()
-    act_local = robot._act_joint_local_t.tolist()
-    ctrl_ids = idx.ctrl_ids.tolist()
-    scale = aterm._scale if isinstance(aterm._scale, float) else None
-    for k, jk in enumerate(jids):
-      a = act_local.index(jk)
-      d.ctrl_of_action[k] = ctrl_ids[a]
-      d.target_of_action[k] = jk
-      d.action_scale[k] = scale if scale is not None else float(aterm._scale[0, k])
-      off = aterm._offset
-      d.action_offset[k] = off if isinstance(off, float) else float(off[0, k])
-    _need(rdata.joint_pos_target.shape[1] == nj, "joint target width")
-    _need(torch.all(rdata.default_joint_pos == rdata.default_joint_pos[:1]).item(),
-          "per-env default joint pos")
-    dj = rdata.default_joint_pos[0].tolist()
-    lim = rdata.soft_joint_pos_limits[0].tolist()
-    for j in range(nj):
-      d.default_joint_pos[j] = dj[j]
-      d.soft_lo[j], d.soft_hi[j] = lim[j]
-    _need(torch.all(rdata.default_joint_vel == 0).item(), "nonzero default joint vel")
-    rs = rdata.default_root_state[0].tolist()
+    m = env.sim.mj_model
+    self._sim(d, env)
+    d.nsite = m.nsite
+    robot = self._joints(d, env)
+    rs = robot.data.default_root_state[0].tolist()
     for i in range(13):
       d.default_root_state[i] = rs[i]
-    origins = scene.env_origins.contiguous()
-    self._keep.append(origins)
-    d.env_origins = _ptr(origins)
     # sensors
     sens = {name: (int(m.sensor_adr[i]), int(m.sensor_dim[i])) for i, name in enumerate(m.names["sensor"])}
     d.imu_lin_vel_adr = d.imu_ang_vel_adr = d.angmom_adr = d.selfcol_found_adr = -1
@@ -525,11 +769,11 @@ class FusedVelocityStep:
   def _orient(self, d, k, kind, p, robot, orient_body):
     ids = p.get("asset_cfg").body_ids if p.get("asset_cfg") is not None else slice(None)
     body = self._body_of(robot, ids)
-    if kind == 2:
+    if kind == MJX_RW_FLAT_ORIENT:
       d.reward_p0[k] = float(p["std"])
     if body is not None:
       return self._same(orient_body if orient_body >= 0 else None, body)
-    _need(kind == 2, "body_ang_vel needs a body")
+    _need(kind == MJX_RW_FLAT_ORIENT, "body_ang_vel needs a body")
     return orient_body
 
   def _feet(self, d, robot, feet_sensor, site_names):
@@ -559,25 +803,25 @@ class FusedVelocityStep:
     d.peak_heights = _ptr(self._peak)
 
   def _terminations(self, d, env):
-    scene, n, dev = env.scene, env.num_envs, torch.device(env.device)
+    scene = env.scene
     tm = env.termination_manager
     d.ntermination = len(tm._term_names)
     for k, (name, c) in enumerate(zip(tm._term_names, tm._term_cfgs)):
       if c.func is mdp.time_out:
-        d.termination_kind[k] = 0
+        d.termination_kind[k] = MJX_TM_TIME_OUT
       elif c.func is mdp.bad_orientation:
-        d.termination_kind[k] = 1
+        d.termination_kind[k] = MJX_TM_BAD_ORIENT
         d.termination_p0[k] = float(c.params["limit_angle"])
       elif c.func is mdp.root_height_below_minimum:
-        d.termination_kind[k] = 3
+        d.termination_kind[k] = MJX_TM_ROOT_HEIGHT
         _need(c.params.get("asset_cfg") is None or c.params["asset_cfg"].name == "robot", "root height asset")
         d.termination_p0[k] = float(c.params["minimum_height"])
       elif c.func in _EXCESSIVE_FORCE:
-        d.termination_kind[k] = 4
+        d.termination_kind[k] = MJX_TM_EXCESSIVE_FORCE
         _need(scene[c.params["sensor_name"]] is self._feet_sensor, "impact sensor is the feet sensor")
         d.termination_p0[k] = float(c.params.get("force_threshold", 2500.0))
       elif c.func is mdp.illegal_contact:
-        d.termination_kind[k] = 2
+        d.termination_kind[k] = MJX_TM_ILLEGAL_CONTACT
         adrs = self._slot_adrs(scene[c.params["sensor_name"]], "found")
         _need(len(adrs) <= MAXC, "illegal contact slots")
         d.nillegal = len(adrs)
@@ -586,36 +830,10 @@ class FusedVelocityStep:
       else:
         raise Unsupported(f"termination {name}")
       d.termination_is_timeout[k] = int(bool(c.time_out))
-    self._term_dones = torch.zeros(max(d.ntermination, 1), n, dtype=torch.bool, device=dev)
-    for k, name in enumerate(tm._term_names):
-      tm._term_dones[name] = self._term_dones[k]
-    d.term_dones = _ptr(self._term_dones, _U8)
-    d.terminated = _ptr(tm._terminated_buf, _U8)
-    d.time_outs = _ptr(tm._truncated_buf, _U8)
-    self.reset_buf = torch.zeros(n, dtype=torch.bool, device=dev)
-    d.reset_buf = _ptr(self.reset_buf, _U8)
-    self._term_names = list(tm._term_names)
-
-  def _reward_buffers(self, d, env):
-    """Episode sums as rows of one [nreward, n] tensor; step reward / reward buffers; timing."""
-    rm, n, dev = env.reward_manager, env.num_envs, torch.device(env.device)
-    self._episode_sums = torch.zeros(max(d.nreward, 1), n, device=dev)
-    for k, name in enumerate(rm._term_names):
-      self._episode_sums[k].copy_(rm._episode_sums[name])
-      rm._episode_sums[name] = self._episode_sums[k]
-    d.episode_sums = _ptr(self._episode_sums)
-    d.step_reward, d.reward_buf = _ptr(rm._step_reward), _ptr(rm._reward_buf)
-    # timing
-    d.step_dt, d.episode_length_s = float(env.step_dt), float(env.max_episode_length_s)
-    # play configs use a 1e9 s episode: clamp into the descriptor's int32 (never reached)
-    d.max_episode_length = min(int(env.max_episode_length), 2 ** 31 - 1)
-    _need(env.episode_length_buf.dtype == torch.int64, "episode length dtype")
-    d.episode_length = _ptr(env.episode_length_buf, _I64)
-    self._reward_names = list(rm._term_names)
+    self._termination_buffers(d, env)
 
   def _events(self, d, env):
     """Reset events (root state + joint offsets) and the optional push interval event."""
-    n, dev = env.num_envs, torch.device(env.device)
     em = env.event_manager
     reset_terms = em._mode_term_cfgs.get("reset", [])
     funcs = [c.func for c in reset_terms]
@@ -629,19 +847,7 @@ class FusedVelocityStep:
           "reset joints over all joints")
     d.reset_joint_pos_range[0], d.reset_joint_pos_range[1] = map(float, rj.params["position_range"])
     d.reset_joint_vel_range[0], d.reset_joint_vel_range[1] = map(float, rj.params["velocity_range"])
-    inter = em._mode_term_cfgs.get("interval", [])
-    _need(len(inter) <= 1, "one interval event")
-    if inter:
-      c = inter[0]
-      _need(c.func is mdp.push_by_setting_velocity and not c.is_global_time, "push event")
-      d.has_push = 1
-      d.push_interval[0], d.push_interval[1] = map(float, c.interval_range_s)
-      for i, (lo, hi) in enumerate(_range6(c.params["velocity_range"])):
-        d.push_vel_range[i][0], d.push_vel_range[i][1] = lo, hi
-      d.push_time_left = _ptr(em._interval_time_left[0])
-    else:
-      self._dummy_push = torch.zeros(n, device=dev)
-      d.push_time_left = _ptr(self._dummy_push)
+    self._push(d, env)
     _need(set(em._mode_term_cfgs) <= {"reset", "interval", "startup"}, "event modes")
 
   def _obs_noise(self, d, env, pol, cri, sens):
@@ -659,39 +865,6 @@ class FusedVelocityStep:
     d.noise_lin_vel, d.noise_ang_vel, d.noise_gravity = (_noise(pol[i][1]) for i in range(3))
     d.noise_joint_pos, d.noise_joint_vel = _noise(pol[3][1]), _noise(pol[4][1])
 
-  def _obs_history(self, d, env, pol, cri):
-    """Observation history / delay: the descriptor's segment tables and the row widths they
-    imply (the single-frame widths stay when no term asks for either)."""
-    self._obs_hist = FusedObsHistory.build(d, env, pol, cri)
-    if self._obs_hist is not None:
-      d.npolicy, d.ncritic = self._obs_hist.widths
-
-  def _io(self, d, env):
-    """Observation buffers, action pointers, seed, log scalars."""
-    om, am, n, dev = env.observation_manager, env.action_manager, env.num_envs, torch.device(env.device)
-    rdata = self._robot.data
-    _need(om.group_obs_dim["policy"] == (d.npolicy,) and om.group_obs_dim["critic"] == (d.ncritic,),
-          "observation dims")
-    self.obs = {"policy": torch.zeros(n, d.npolicy, device=dev),
-                "critic": torch.zeros(n, d.ncritic, device=dev)}
-    d.obs_policy, d.obs_critic = _ptr(self.obs["policy"]), _ptr(self.obs["critic"])
-    if self._obs_hist is not None:
-      self._obs_hist.seed(self.obs)
-    d.action, d.prev_action = _ptr(am._action), _ptr(am._prev_action)
-    d.prev_prev_action, d.joint_pos_target = _ptr(am._prev_prev_action), _ptr(rdata.joint_pos_target)
-    d.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    # logs
-    self.log_reward = torch.zeros(max(d.nreward, 1), device=dev)
-    self.log_term = torch.zeros(max(d.ntermination, 1), device=dev)
-    self.log_cmd = torch.zeros(2, device=dev)
-    self.log_metric = torch.zeros(NMETRIC, device=dev)
-    self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-    d.log_reward, d.log_termination = _ptr(self.log_reward), _ptr(self.log_term)
-    d.log_command, d.log_metric = _ptr(self.log_cmd), _ptr(self.log_metric)
-    d.step_counter = _ptr(self.step_counter, _U64)
-    self._keep.extend([self._term_dones, self.reset_buf, self._episode_sums])
-    return d
-
   @staticmethod
   def _same(prev, new):
     _need(prev is None or prev == new, "terms disagree on feet/body")
@@ -704,11 +877,6 @@ class FusedVelocityStep:
     ids = ids.tolist() if isinstance(ids, torch.Tensor) else list(ids)
     _need(len(ids) == 1, "single body")
     return int(robot.indexing.body_ids[ids[0]])
-
-  @staticmethod
-  def _slot_adrs(sensor, field):
-    _need(getattr(sensor, "_num_slots", 1) == 1, "one contact slot per primary")
-    return [adr for _, f, adr, _ in sensor._slots if f == field]
 
   @staticmethod
   def _set_command_ranges(d, cc):
@@ -739,107 +907,43 @@ class FusedVelocityStep:
     return True
 
   def release(self) -> None:
-    """Hand the air-time buffers back to the torch ContactSensor.update path: the engine
-    stops updating them (n = 0).  Called when the env drops or replaces this fused step
-    (enable_graph); without it a later torch-manager step would advance air time twice per
-    substep."""
-    if getattr(self, "_obs_hist", None) is not None:
-      # the observation history / delay state goes back to the manager's buffers
-      self._obs_hist.hand_back(self.obs)
-      self._obs_hist = None
-    release_explicit_actuators(self)
+    """As the base, and the air-time buffers go back to the torch ContactSensor.update path:
+    the engine stops updating them (n = 0); without it a later torch-manager step would
+    advance air time twice per substep."""
+    super().release()
     if not getattr(self, "_engine_air", False):
       return
     sim = self.env.sim
     if getattr(sim, "_sim", None) is not None and sim._sim.value:
-      stream = ctypes.c_void_p(torch.cuda.current_stream(sim._torch_device).cuda_stream)
-      check(lib().mjx_sim_track_air_time(sim._sim, 0, None, None, None, None, None, None, stream))
+      check(lib().mjx_sim_track_air_time(sim._sim, 0, None, None, None, None, None, None, self._stream()))
     self._feet_sensor.engine_owned = False
     self._engine_air = False
 
-  # ------------------------------------------------------------------ device handle
-  def upload(self):
-    """(Re)create the device copy of the descriptor (after a curriculum changed command
-    ranges or reward weights)."""
-    self._set_command_ranges(self._desc, self._cmd_term.cfg)
-    for k, c in enumerate(self.env.reward_manager._term_cfgs):
-      self._desc.reward_weight[k] = float(c.weight)
-    if self._task is not None:
-      self._L.mjx_task_destroy(self._task)
-    h = ctypes.c_void_p()
-    rc = self._L.mjx_task_create(ctypes.byref(self._desc), ctypes.byref(h))
-    if rc != 0:
-      raise MjxError(self._L.mjx_task_last_error().decode())
-    self._task = h
-
-  def __del__(self):
-    # no hand-back from a finaliser: it may run while the interpreter tears the manager's
-    # tensors down (enable_graph releases explicitly)
-    self._obs_hist = None
-    try:
-      self.release()
-    except Exception:
-      pass
-    try:
-      if self._task is not None:
-        self._L.mjx_task_destroy(self._task)
-    except Exception:
-      pass
-
-  def _ok(self, rc):
-    if rc != 0:
-      raise MjxError(self._L.mjx_task_last_error().decode())
+  def _refresh_desc(self):
+    self._set_command_ranges(self._desc, self._cmd_term.cfg)  # the command curriculum
 
   # ------------------------------------------------------------------ the env step
-  # False while the env records a graph whose replays run apply_action() before them (the
-  # action kernel then reads the caller's tensor: no copy into a static input buffer)
-  action_in_step = True
-
-  def apply_action(self, action: torch.Tensor):
-    stream = ctypes.c_void_p(torch.cuda.current_stream(self.env.sim._torch_device).cuda_stream)
-    self._ok(self._L.mjx_task_action(self._task, ctypes.c_void_p(action.data_ptr()), stream))
-
-  def step(self, action: torch.Tensor):
-    env, L, sim = self.env, self._L, self.env.sim
-    stream = ctypes.c_void_p(torch.cuda.current_stream(sim._torch_device).cuda_stream)
-    if self.action_in_step:
-      self._ok(L.mjx_task_action(self._task, ctypes.c_void_p(action.data_ptr()), stream))
+  def _substeps(self, stream):
     if self._engine_air:
       # the engine updates the feet air times every substep (mjx_sim_track_air_time) and
-      # nothing reads mjData between substeps: one mjx_step of `decimation` substeps, whose
-      # full mjData outputs (frames, contacts, forces) are written after the last only
-      sim.step(nsubstep=env.cfg.decimation)
-    else:
-      for _ in range(env.cfg.decimation):
-        sim.step()
-        self._ok(L.mjx_task_substep(self._task, stream))
-    self._ok(L.mjx_task_post(self._task, stream))
+      # nothing reads mjData between substeps
+      return super()._substeps(stream)
+    for _ in range(self.env.cfg.decimation):
+      self.env.sim.step()
+      self._call("substep", stream)
+
+  def _before_reset(self):
     # per-env curriculum terms (terrain levels) of the resetting envs, before the reset
     # events read the env origins (the reference's _reset_idx order)
-    cur = env.curriculum_manager
+    env, cur = self.env, self.env.curriculum_manager
     cur.compute_masked(self.reset_buf)
     for name, state in getattr(cur, "_curriculum_state", {}).items():
       if isinstance(state, torch.Tensor):
         env.extras.setdefault("log", {})[f"Curriculum/{name}"] = state
-    mask = ctypes.c_void_p(self.reset_buf.data_ptr())
-    check(lib().mjx_reset(sim._sim, mask, stream))
-    self._ok(L.mjx_task_reset(self._task, stream))
-    if self._engine_act is not None:  # delay history of the reset envs: cleared, one frame
-      self._engine_act.reset_masked(self.reset_buf)
-    check(lib().mjx_forward_masked(sim._sim, mask, stream))
-    self._ok(L.mjx_task_observe(self._task, stream))
-    tm = env.termination_manager
-    return self.obs, env.reward_manager._reward_buf, tm._terminated_buf, tm._truncated_buf
 
   def log(self) -> dict:
-    """Episode logs as device scalars under the reference's keys."""
-    out = {}
-    for k, name in enumerate(self._reward_names):
-      out["Episode_Reward/" + name] = self.log_reward[k]
-    for k, name in enumerate(self._term_names):
-      out["Episode_Termination/" + name] = self.log_term[k]
-    out["Metrics/twist/error_vel_xy"] = self.log_cmd[0]
-    out["Metrics/twist/error_vel_yaw"] = self.log_cmd[1]
+    out = super().log()
+    out[self._CMD_LOG[0]], out[self._CMD_LOG[1]] = self.log_cmd[0], self.log_cmd[1]
     for i, key in enumerate(_METRIC_KEYS):
       if self._metric_active[i]:
         out[key] = self.log_metric[i]
@@ -847,13 +951,14 @@ class FusedVelocityStep:
 
 
 # ============================================================================ jump task
-CMD_JUMP = 1
 _JUMP_REWARD_KIND = {
-  jump.explosive_takeoff: 15, jump.synchronized_extension: 16, jump.vertical_impulse: 17,
-  jump.air_time_bonus: 18, jump.symmetric_landing: 20, mdp.action_acc_l2: 21,
-  mdp.joint_torques_l2: 22, mdp.is_alive: 23, mdp.flat_orientation: 2,
-  mdp.angular_momentum_penalty: 5, mdp.soft_landing: 12, mdp.action_rate_l2: 7,
-  mdp.joint_pos_limits: 6,
+  jump.explosive_takeoff: MJX_RW_EXPLOSIVE_TAKEOFF, jump.synchronized_extension: MJX_RW_SYNC_EXTENSION,
+  jump.vertical_impulse: MJX_RW_VERTICAL_IMPULSE, jump.air_time_bonus: MJX_RW_AIR_TIME_BONUS,
+  jump.symmetric_landing: MJX_RW_SYMMETRIC_LANDING, mdp.action_acc_l2: MJX_RW_ACTION_ACC,
+  mdp.joint_torques_l2: MJX_RW_JOINT_TORQUES, mdp.is_alive: MJX_RW_IS_ALIVE,
+  mdp.flat_orientation: MJX_RW_FLAT_ORIENT, mdp.angular_momentum_penalty: MJX_RW_ANGMOM,
+  mdp.soft_landing: MJX_RW_SOFT_LANDING, mdp.action_rate_l2: MJX_RW_ACTION_RATE,
+  mdp.joint_pos_limits: MJX_RW_JOINT_POS_LIMITS,
 }
 _JUMP_POLICY = [("base_lin_vel", mdp.builtin_sensor), ("base_ang_vel", mdp.builtin_sensor),
                 ("projected_gravity", mdp.projected_gravity), ("joint_pos", mdp.joint_pos_rel),
@@ -875,7 +980,7 @@ class FusedJumpStep(FusedVelocityStep):
     d = TaskDesc()
     robot, sens = self._base(d, env)
     scene, nj, dev = env.scene, d.njoint, torch.device(env.device)
-    d.command_kind = CMD_JUMP
+    d.command_kind = MJX_CMD_JUMP
     idx = robot.indexing
     ctrl_ids = idx.ctrl_ids.tolist()
     _need(len(ctrl_ids) == nj and d.nu == nj, "one actuator per joint")
@@ -908,34 +1013,34 @@ class FusedJumpStep(FusedVelocityStep):
       if "sensor_name" in p and p["sensor_name"] != "robot/root_angmom":
         _need(p["sensor_name"] == feet_sensor, f"{name}: feet sensor")
       if isinstance(f, jump.jump_height_reward):
-        kind = 14
+        kind = MJX_RW_JUMP_HEIGHT
         d.reward_p0[k], d.reward_p1[k] = float(p["target_height"]), float(p["std"])
         self._jump_height = f
-        self._metric_active[5] = self._metric_active[6] = c.weight != 0.0
+        self._metric_active[MJX_MT_PEAK_JUMP] = self._metric_active[MJX_MT_JUMP_HEIGHT] = c.weight != 0.0
       elif isinstance(f, jump.landing_balance):
-        kind = 19
+        kind = MJX_RW_LANDING_BALANCE
         d.reward_p0[k] = float(p.get("stability_time", 0.5))
         _need(abs(f.step_dt - env.step_dt) < 1e-12, "landing timer dt")
         self._landing = f
-        self._metric_active[7] = c.weight != 0.0
+        self._metric_active[MJX_MT_LANDING_SUCCESS] = c.weight != 0.0
       else:
         _need(f in _JUMP_REWARD_KIND, f"jump reward term {name}")
         kind = _JUMP_REWARD_KIND[f]
-        if kind == 2:
+        if kind == MJX_RW_FLAT_ORIENT:
           orient_body = self._orient(d, k, kind, p, robot, orient_body)
-        elif kind == 5:
+        elif kind == MJX_RW_ANGMOM:
           d.angmom_adr = sens[p["sensor_name"]][0]
-        elif kind == 12:
+        elif kind == MJX_RW_SOFT_LANDING:
           d.reward_p0[k] = float(p.get("command_threshold", 0.05))
           _need(p.get("command_name") is None, "jump soft_landing is ungated")
           d.reward_p1[k] = 1.0
-        elif kind == 15:
+        elif kind == MJX_RW_EXPLOSIVE_TAKEOFF:
           d.reward_p0[k] = float(p.get("power_threshold", 500.0))
           ac = p.get("asset_cfg")
           ids = ac.joint_ids if ac is not None else slice(None)
           ids = list(range(nj)) if isinstance(ids, slice) else [int(i) for i in ids]
           d.explosive_joints = sum(1 << i for i in ids)
-        elif kind == 18:
+        elif kind == MJX_RW_AIR_TIME_BONUS:
           d.reward_p0[k] = float(p.get("min_air_time", 0.2))
       d.reward_kind[k] = kind
       if c.weight != 0.0 and kind in _METRIC_OF_KIND:
@@ -971,32 +1076,10 @@ class FusedJumpStep(FusedVelocityStep):
       _need(pol[i][1].noise is None, "noise beyond the proprioceptive terms")
     d.npolicy = 9 + 3 * nj + 2 + 2 * d.nfeet + 1
     d.ncritic = d.npolicy + 4 * d.nfeet
-    self._obs_history(d, env, pol, cri)
-    self._io(d, env)
+    self._io(d, env, pol, cri, NMETRIC)
     return d
 
-  def upload(self):
-    """Curricula move the target height (progressive_jump_height) and reward weights."""
-    self._desc.jump_target_height = float(self._cmd_term.cfg.target_height)
-    for k, c in enumerate(self.env.reward_manager._term_cfgs):
-      self._desc.reward_weight[k] = float(c.weight)
-    if self._task is not None:
-      self._L.mjx_task_destroy(self._task)
-    h = ctypes.c_void_p()
-    rc = self._L.mjx_task_create(ctypes.byref(self._desc), ctypes.byref(h))
-    if rc != 0:
-      raise MjxError(self._L.mjx_task_last_error().decode())
-    self._task = h
+  _CMD_LOG = ("Metrics/jump/target_height", "Metrics/jump/peak_height")
 
-  def log(self) -> dict:
-    out = {}
-    for k, name in enumerate(self._reward_names):
-      out["Episode_Reward/" + name] = self.log_reward[k]
-    for k, name in enumerate(self._term_names):
-      out["Episode_Termination/" + name] = self.log_term[k]
-    out["Metrics/jump/target_height"] = self.log_cmd[0]
-    out["Metrics/jump/peak_height"] = self.log_cmd[1]
-    for i, key in enumerate(_METRIC_KEYS):
-      if self._metric_active[i]:
-        out[key] = self.log_metric[i]
-    return out
+  def _refresh_desc(self):  # progressive_jump_height moves the target height
+    self._desc.jump_target_height = float(self._cmd_term.cfg.target_height)

@@ -13,6 +13,10 @@ Otherwise it returns None and the env keeps the torch manager path.
 The kernels read and write the managers' own tensors (action histories, MotionCommand
 time steps / relative body targets / failure bins / metrics, episode sums, termination
 flags, push timers), so every accessor of the reference API keeps working.
+
+The binding, the device handle, the step itself and the descriptor fields shared with the
+velocity family come from `fused.FusedStepBase`; this module adds the tracking descriptor,
+its kind tables (the header's `MJX_TR_*` / `MJX_TT_*`) and the tracking part of `_make_desc`.
 """
 
 from __future__ import annotations
@@ -23,17 +27,23 @@ import torch
 
 from . import mdp
 from . import tracking as trk
-from ._lib import MjxError, check, lib
-from .fused import (MAXJ, MAXT, FusedObsHistory, ObsState, Unsupported, _f2, _f62, _FP, _I64, _need,
-                    _noise, _ptr, _range6, _U8, _U64, bind_explicit_actuators,
-                    explicit_actuator_entities, release_explicit_actuators)
+from .fused import (MAXJ, MAXT, FusedStepBase, ObsState, _f2, _f62, _FP, _I64, _need, _noise, _ptr,
+                    _range6, _U8, _U64)
 
-MAXB, NMETRIC = 32, 13
+# include/mjx355_task.h by name (tests/test_task_constants.py holds them against the header)
+MJX_TRACK_MAX_BODIES, MJX_TRACK_MAX_BINS, MJX_TRACK_NMETRIC = 32, 1024, 13
+(MJX_TR_ANCHOR_POS, MJX_TR_ANCHOR_ORI, MJX_TR_BODY_POS, MJX_TR_BODY_ORI, MJX_TR_BODY_LIN_VEL,
+ MJX_TR_BODY_ANG_VEL, MJX_TR_ACTION_RATE, MJX_TR_JOINT_LIMIT, MJX_TR_SELF_COLLISION) = range(9)
+(MJX_TT_TIME_OUT, MJX_TT_ANCHOR_POS_Z, MJX_TT_ANCHOR_ORI, MJX_TT_BODY_POS_Z, MJX_TT_ANCHOR_POS,
+ MJX_TT_BODY_POS) = range(6)
+
+MAXB, NMETRIC = MJX_TRACK_MAX_BODIES, MJX_TRACK_NMETRIC
 _I32 = ctypes.c_int
 METRIC_NAMES = ("error_anchor_pos", "error_anchor_rot", "error_anchor_lin_vel",
                 "error_anchor_ang_vel", "error_body_pos", "error_body_rot", "error_body_lin_vel",
                 "error_body_ang_vel", "error_joint_pos", "error_joint_vel", "sampling_entropy",
                 "sampling_top1_prob", "sampling_top1_bin")
+assert len(METRIC_NAMES) == NMETRIC
 
 
 class TrackDesc(ctypes.Structure):
@@ -88,15 +98,17 @@ class TrackDesc(ctypes.Structure):
   ]
 
 
-_BODY_REWARDS = {trk.motion_relative_body_position_error_exp: 2,
-                 trk.motion_relative_body_orientation_error_exp: 3,
-                 trk.motion_global_body_linear_velocity_error_exp: 4,
-                 trk.motion_global_body_angular_velocity_error_exp: 5}
-_REWARDS = {trk.motion_global_anchor_position_error_exp: 0,
-            trk.motion_global_anchor_orientation_error_exp: 1, **_BODY_REWARDS,
-            mdp.action_rate_l2: 6, mdp.joint_pos_limits: 7, mdp.self_collision_cost: 8}
-_TERMS = {mdp.time_out: 0, trk.bad_anchor_pos_z_only: 1, trk.bad_anchor_ori: 2,
-          trk.bad_motion_body_pos_z_only: 3, trk.bad_anchor_pos: 4, trk.bad_motion_body_pos: 5}
+_BODY_REWARDS = {trk.motion_relative_body_position_error_exp: MJX_TR_BODY_POS,
+                 trk.motion_relative_body_orientation_error_exp: MJX_TR_BODY_ORI,
+                 trk.motion_global_body_linear_velocity_error_exp: MJX_TR_BODY_LIN_VEL,
+                 trk.motion_global_body_angular_velocity_error_exp: MJX_TR_BODY_ANG_VEL}
+_REWARDS = {trk.motion_global_anchor_position_error_exp: MJX_TR_ANCHOR_POS,
+            trk.motion_global_anchor_orientation_error_exp: MJX_TR_ANCHOR_ORI, **_BODY_REWARDS,
+            mdp.action_rate_l2: MJX_TR_ACTION_RATE, mdp.joint_pos_limits: MJX_TR_JOINT_LIMIT,
+            mdp.self_collision_cost: MJX_TR_SELF_COLLISION}
+_TERMS = {mdp.time_out: MJX_TT_TIME_OUT, trk.bad_anchor_pos_z_only: MJX_TT_ANCHOR_POS_Z,
+          trk.bad_anchor_ori: MJX_TT_ANCHOR_ORI, trk.bad_motion_body_pos_z_only: MJX_TT_BODY_POS_Z,
+          trk.bad_anchor_pos: MJX_TT_ANCHOR_POS, trk.bad_motion_body_pos: MJX_TT_BODY_POS}
 _CRITIC = [("command", mdp.generated_commands), ("motion_anchor_pos_b", trk.motion_anchor_pos_b),
            ("motion_anchor_ori_b", trk.motion_anchor_ori_b), ("body_pos", trk.robot_body_pos_b),
            ("body_ori", trk.robot_body_ori_b), ("base_lin_vel", mdp.builtin_sensor),
@@ -104,97 +116,28 @@ _CRITIC = [("command", mdp.generated_commands), ("motion_anchor_pos_b", trk.moti
            ("joint_vel", mdp.joint_vel_rel), ("actions", mdp.last_action)]
 
 
-class FusedTrackingStep:
+class FusedTrackingStep(FusedStepBase):
   """One env step of the tracking task as fused HIP launches (see module docstring)."""
 
-  @classmethod
-  def build(cls, env):
-    try:
-      return cls(env)
-    except Unsupported as e:
-      env._fused_unsupported = str(e)
-      return None
-
-  def __init__(self, env):
-    self.env = env
-    L = lib()
-    _need(hasattr(L, "mjx_track_desc_size"), "library without the tracking kernels")
-    L.mjx_track_desc_size.restype = ctypes.c_size_t
-    _need(L.mjx_track_desc_size() == ctypes.sizeof(TrackDesc), "mjxTrackDesc layout mismatch")
-    L.mjx_track_create.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    L.mjx_track_action.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    for n in ("mjx_track_post", "mjx_track_reset", "mjx_track_observe"):
-      getattr(L, n).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.mjx_track_destroy.argtypes = [ctypes.c_void_p]
-    L.mjx_track_last_error.restype = ctypes.c_char_p
-    self._L = L
-    self._keep = []
-    self._task = None
-    self._desc = self._make_desc(env)
-    self._engine_act = bind_explicit_actuators(self, self._desc)
-    try:
-      self.upload()
-    except Exception:
-      release_explicit_actuators(self)  # the env falls back in torch mode
-      raise
+  PREFIX, DESC = "mjx_track", TrackDesc
+  SIM_FIELDS = ("qpos", "qvel", "ctrl", "xpos", "xquat", "cvel", "subtree_com", "sensordata")
 
   # ------------------------------------------------------------------ descriptor
   def _make_desc(self, env):
     d = TrackDesc()
-    sim, scene, m = env.sim, env.scene, env.sim.mj_model
-    dev = torch.device(env.device)
-    sd = sim.data
-    n = env.num_envs
-    d.nworld, d.nq, d.nv, d.nu = n, m.nq, m.nv, m.nu
-    d.nsensordata, d.nbody = m.nsensordata, m.nbody
-    for f in ("qpos", "qvel", "ctrl", "xpos", "xquat", "cvel", "subtree_com", "sensordata"):
-      setattr(d, f, _ptr(getattr(sd, f)))
+    scene, m = env.scene, env.sim.mj_model
+    dev, n = torch.device(env.device), env.num_envs
+    self._sim(d, env)
     # command
     cm = env.command_manager
     _need(list(getattr(cm, "_terms", {}).keys()) == ["motion"], "single 'motion' command")
     c = cm._terms["motion"]
     _need(isinstance(c, trk.MotionCommand), "MotionCommand")
     cc = c.cfg
-    # actions
-    am = env.action_manager
-    _need(len(am._terms) == 1, "one action term")
-    (aterm,) = am._terms.values()
-    _need(isinstance(aterm, mdp.JointPositionAction), "JointPositionAction only")
-    robot = aterm._asset
+    # actions (encoder bias included: the kernels read it per env)
+    robot = self._joints(d, env)
     _need(robot is c.robot, "command and action on one entity")
-    self._explicit = explicit_actuator_entities(env, robot)
-    rdata = robot.data
-    idx = robot.indexing
-    nj = len(idx.joint_q_adr)
-    _need(nj <= MAXJ and aterm.action_dim == nj, "action dim == actuated joints")
-    d.root_body = int(idx.root_body_id)
-    d.free_q_adr, d.free_v_adr = int(idx.free_joint_q_adr[0]), int(idx.free_joint_v_adr[0])
-    d.njoint = nj
-    jq, jv = idx.joint_q_adr.tolist(), idx.joint_v_adr.tolist()
-    for j in range(nj):
-      d.joint_q_adr[j], d.joint_v_adr[j] = jq[j], jv[j]
-    jids = aterm._joint_ids.tolist()
-    act_local = robot._act_joint_local_t.tolist()
-    ctrl_ids = idx.ctrl_ids.tolist()
-    off = aterm._offset
-    _need(isinstance(off, float) or bool(torch.all(off == off[:1]).item()), "per-env action offset")
-    for k, jk in enumerate(jids):
-      d.ctrl_of_action[k] = ctrl_ids[act_local.index(jk)]
-      d.target_of_action[k] = jk
-      d.action_scale[k] = aterm._scale if isinstance(aterm._scale, float) else float(aterm._scale[0, k])
-      d.action_offset[k] = off if isinstance(off, float) else float(off[0, k])
-    _need(torch.all(rdata.default_joint_pos == rdata.default_joint_pos[:1]).item(), "per-env default joint pos")
-    _need(torch.all(rdata.soft_joint_pos_limits == rdata.soft_joint_pos_limits[:1]).item(), "per-env soft limits")
-    _need(torch.all(rdata.default_joint_vel == 0).item(), "nonzero default joint vel")
-    dj = rdata.default_joint_pos[0].tolist()
-    lim = rdata.soft_joint_pos_limits[0].tolist()
-    for j in range(nj):
-      d.default_joint_pos[j] = dj[j]
-      d.soft_lo[j], d.soft_hi[j] = lim[j]
-    d.encoder_bias = _ptr(rdata.encoder_bias)
-    origins = scene.env_origins.contiguous()
-    self._keep.append(origins)
-    d.env_origins = _ptr(origins)
+    idx, nj = robot.indexing, d.njoint
     # motion
     mo = c.motion
     body_ids = idx.body_ids.tolist()
@@ -264,17 +207,17 @@ class FusedTrackingStep:
       kind = _REWARDS[f]
       d.reward_kind[k] = kind
       d.reward_weight[k] = float(cfg.weight)
-      if kind <= 5:
+      if kind <= MJX_TR_BODY_ANG_VEL:  # the six exp-kernel tracking terms
         _need(p.get("command_name") == "motion", "reward command name")
         d.reward_std[k] = float(p["std"])
       if kind in _BODY_REWARDS.values():
         d.reward_bodies[k] = bodies_mask(p.get("body_names"))
         _need(d.reward_bodies[k] != 0, "empty reward body set")
-      if kind == 7:
+      if kind == MJX_TR_JOINT_LIMIT:
         a = p.get("asset_cfg")
         _need(a is None or isinstance(a.joint_ids, slice), "joint_pos_limits over all joints")
-      if kind == 8:
-        adrs = self._found_adrs(scene[p["sensor_name"]])
+      if kind == MJX_TR_SELF_COLLISION:
+        adrs = self._slot_adrs(scene[p["sensor_name"]], "found")
         _need(len(adrs) == 1, "self-collision sensor with one slot")
         d.selfcol_found_adr = adrs[0]
     # terminations
@@ -286,47 +229,18 @@ class FusedTrackingStep:
       kind = _TERMS[cfg.func]
       d.termination_kind[k] = kind
       d.termination_is_timeout[k] = int(bool(cfg.time_out))
-      if kind > 0:
+      if kind != MJX_TT_TIME_OUT:
         _need(cfg.params.get("command_name") == "motion", "termination command name")
         d.termination_threshold[k] = float(cfg.params["threshold"])
-      if kind in (3, 5):
+      if kind in (MJX_TT_BODY_POS_Z, MJX_TT_BODY_POS):
         d.termination_bodies[k] = bodies_mask(cfg.params.get("body_names"))
-    self._term_dones = torch.zeros(max(d.ntermination, 1), n, dtype=torch.bool, device=dev)
-    for k, name in enumerate(tm._term_names):
-      tm._term_dones[name] = self._term_dones[k]
-    d.term_dones = _ptr(self._term_dones, _U8)
-    d.terminated = _ptr(tm._terminated_buf, _U8)
-    d.time_outs = _ptr(tm._truncated_buf, _U8)
-    self.reset_buf = torch.zeros(n, dtype=torch.bool, device=dev)
+    self._termination_buffers(d, env)
     self._resample_mask = torch.zeros(n, dtype=torch.bool, device=dev)
-    d.reset_buf, d.resample_mask = _ptr(self.reset_buf, _U8), _ptr(self._resample_mask, _U8)
-    self._episode_sums = torch.zeros(max(d.nreward, 1), n, device=dev)
-    for k, name in enumerate(rm._term_names):
-      self._episode_sums[k].copy_(rm._episode_sums[name])
-      rm._episode_sums[name] = self._episode_sums[k]
-    d.episode_sums = _ptr(self._episode_sums)
-    d.step_reward, d.reward_buf = _ptr(rm._step_reward), _ptr(rm._reward_buf)
-    d.step_dt, d.episode_length_s = float(env.step_dt), float(env.max_episode_length_s)
-    # play configs use a 1e9 s episode: clamp into the descriptor's int32 (never reached)
-    d.max_episode_length = min(int(env.max_episode_length), 2 ** 31 - 1)
-    _need(env.episode_length_buf.dtype == torch.int64, "episode length dtype")
-    d.episode_length = _ptr(env.episode_length_buf, _I64)
+    d.resample_mask = _ptr(self._resample_mask, _U8)
+    self._reward_buffers(d, env)
     # events: startup (done), interval push; no reset-mode terms (the command's RSI resets)
-    em = env.event_manager
-    _need(set(em._mode_term_cfgs) <= {"interval", "startup"}, "event modes")
-    inter = em._mode_term_cfgs.get("interval", [])
-    _need(len(inter) <= 1, "one interval event")
-    if inter:
-      ci = inter[0]
-      _need(ci.func is mdp.push_by_setting_velocity and not ci.is_global_time, "push event")
-      d.has_push = 1
-      d.push_interval[0], d.push_interval[1] = map(float, ci.interval_range_s)
-      for i, (lo, hi) in enumerate(_range6(ci.params["velocity_range"])):
-        d.push_vel_range[i][0], d.push_vel_range[i][1] = lo, hi
-      d.push_time_left = _ptr(em._interval_time_left[0])
-    else:
-      self._dummy_push = torch.zeros(n, device=dev)
-      d.push_time_left = _ptr(self._dummy_push)
+    _need(set(env.event_manager._mode_term_cfgs) <= {"interval", "startup"}, "event modes")
+    self._push(d, env)
     # observations
     om = env.observation_manager
     groups = om._group_obs_term_names
@@ -370,102 +284,12 @@ class FusedTrackingStep:
       _need(polf[key].noise is None, "noise on command/actions")
     d.ncritic = 5 * nj + 9 * nmb + 15
     d.npolicy = 5 * nj + 9 + 3 * d.policy_anchor_pos + 3 * d.policy_lin_vel
-    # observation history / delay: segment tables and the row widths they imply
-    self._obs_hist = FusedObsHistory.build(d, env, pol, cri)
-    if self._obs_hist is not None:
-      d.npolicy, d.ncritic = self._obs_hist.widths
-    _need(om.group_obs_dim["policy"] == (d.npolicy,) and om.group_obs_dim["critic"] == (d.ncritic,),
-          "observation dims")
-    self.obs = {"policy": torch.zeros(n, d.npolicy, device=dev),
-                "critic": torch.zeros(n, d.ncritic, device=dev)}
-    d.obs_policy, d.obs_critic = _ptr(self.obs["policy"]), _ptr(self.obs["critic"])
-    if self._obs_hist is not None:
-      self._obs_hist.seed(self.obs)
-    d.action, d.prev_action = _ptr(am._action), _ptr(am._prev_action)
-    d.prev_prev_action, d.joint_pos_target = _ptr(am._prev_prev_action), _ptr(rdata.joint_pos_target)
-    d.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    # logs
-    self.log_reward = torch.zeros(max(d.nreward, 1), device=dev)
-    self.log_term = torch.zeros(max(d.ntermination, 1), device=dev)
-    self.log_metric = torch.zeros(NMETRIC, device=dev)
-    self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-    d.log_reward, d.log_termination = _ptr(self.log_reward), _ptr(self.log_term)
-    d.log_metric = _ptr(self.log_metric)
-    d.step_counter = _ptr(self.step_counter, _U64)
-    self._reward_names, self._term_names = list(rm._term_names), list(tm._term_names)
-    self._keep.extend([self._term_dones, self.reset_buf, self._resample_mask, self._episode_sums,
-                       self._metrics, self._sampling])
+    self._io(d, env, pol, cri, NMETRIC)
+    self._keep.extend([self._resample_mask, self._metrics, self._sampling])
     return d
 
-  @staticmethod
-  def _found_adrs(sensor):
-    _need(getattr(sensor, "_num_slots", 1) == 1, "one contact slot per primary")
-    return [adr for _, f, adr, _ in sensor._slots if f == "found"]
-
-  # ------------------------------------------------------------------ device handle
-  def upload(self):
-    """(Re)create the device copy of the descriptor (after a curriculum changed reward
-    weights)."""
-    for k, c in enumerate(self.env.reward_manager._term_cfgs):
-      self._desc.reward_weight[k] = float(c.weight)
-    if self._task is not None:
-      self._L.mjx_track_destroy(self._task)
-    h = ctypes.c_void_p()
-    rc = self._L.mjx_track_create(ctypes.byref(self._desc), ctypes.byref(h))
-    if rc != 0:
-      raise MjxError(self._L.mjx_track_last_error().decode())
-    self._task = h
-
-  def release(self) -> None:
-    """Called when the env drops or replaces this fused step (enable_graph): the observation
-    history / delay state goes back to the manager's buffers."""
-    if getattr(self, "_obs_hist", None) is not None:
-      self._obs_hist.hand_back(self.obs)
-      self._obs_hist = None
-    release_explicit_actuators(self)
-
-  def __del__(self):
-    try:
-      if self._task is not None:
-        self._L.mjx_track_destroy(self._task)
-    except Exception:
-      pass
-
-  def _ok(self, rc):
-    if rc != 0:
-      raise MjxError(self._L.mjx_track_last_error().decode())
-
-  # ------------------------------------------------------------------ the env step
-  action_in_step = True  # as FusedVelocityStep.action_in_step
-
-  def apply_action(self, action: torch.Tensor):
-    stream = ctypes.c_void_p(torch.cuda.current_stream(self.env.sim._torch_device).cuda_stream)
-    self._ok(self._L.mjx_track_action(self._task, ctypes.c_void_p(action.data_ptr()), stream))
-
-  def step(self, action: torch.Tensor):
-    env, L, sim = self.env, self._L, self.env.sim
-    stream = ctypes.c_void_p(torch.cuda.current_stream(sim._torch_device).cuda_stream)
-    if self.action_in_step:
-      self._ok(L.mjx_track_action(self._task, ctypes.c_void_p(action.data_ptr()), stream))
-    sim.step(nsubstep=env.cfg.decimation)  # mjData outputs written after the last substep
-    self._ok(L.mjx_track_post(self._task, stream))
-    mask = ctypes.c_void_p(self.reset_buf.data_ptr())
-    check(lib().mjx_reset(sim._sim, mask, stream))
-    self._ok(L.mjx_track_reset(self._task, stream))
-    if self._engine_act is not None:  # delay history of the reset envs: cleared, one frame
-      self._engine_act.reset_masked(self.reset_buf)
-    check(lib().mjx_forward_masked(sim._sim, mask, stream))
-    self._ok(L.mjx_track_observe(self._task, stream))
-    tm = env.termination_manager
-    return self.obs, env.reward_manager._reward_buf, tm._terminated_buf, tm._truncated_buf
-
   def log(self) -> dict:
-    """Episode logs as device scalars under the reference's keys."""
-    out = {}
-    for k, name in enumerate(self._reward_names):
-      out["Episode_Reward/" + name] = self.log_reward[k]
-    for k, name in enumerate(self._term_names):
-      out["Episode_Termination/" + name] = self.log_term[k]
+    out = super().log()
     for k, name in enumerate(METRIC_NAMES):
       out["Metrics/motion/" + name] = self.log_metric[k]
     return out
