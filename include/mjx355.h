@@ -74,6 +74,13 @@ typedef struct mjxModelDesc_ {
   int nq, nv, nu, nbody, njnt, ngeom, nsite, nsensor, nsensordata, npair;
   int nhfield, nhfielddata, nlevel;
   int nmaskword; /* 32-bit words per contact-sensor geom mask: ceil(ngeom / 32) */
+  /* cone: 0 pyramidal, 1 elliptic (anything else is refused).  Elliptic: a contact of dimension
+   * dim in {3, 4, 6} has dim constraint rows -- normal, two tangents, torsional, two rolling --
+   * instead of the pyramid's 2 (dim - 1); nefc and every row counter (mjx_sim_stats) count
+   * them, within the same capacities.  The outputs "contact_force" and "contact_torque" (and a
+   * contact sensor's force / torque fields) are then the row forces themselves in the contact
+   * frame: (f_0, f_1, f_2) and (f_3, f_4, f_5), zero below the dimension.  An elliptic model runs
+   * the generic step kernels only. */
   int iterations, ls_iterations, integrator, cone;
   /* contact sensors: matches per sensor and world considered, the first contact_maxmatch in
    * contact order (>= 1; SimulationCfg.contact_sensor_maxmatch, sim/sim.py:95,141) */

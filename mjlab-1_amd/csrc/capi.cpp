@@ -93,17 +93,19 @@ struct Capacity {
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
 static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid, int neq,
-                         int max_condim, const char* too_big, Capacity& c) {
+                         int max_condim, int cone, const char* too_big, Capacity& c) {
   c.d = d;
   for (int i = 0; i < 3; i++) {
     // (phases A and C hold the contacts' friction coefficients: five each with torsional or
     // rolling contacts in the model)
-    c.lds[i] = mjx::make_lds(d, i, false, mjx::con_mu_width(max_condim));
+    // (and an elliptic model's row slots carry the contact grouping: carve.h make_lds)
+    c.lds[i] = mjx::make_lds(d, i, false, mjx::con_mu_width(max_condim), cone);
     if ((size_t)c.lds[i].total * 4 > 160 * 1024) return fail(too_big);
   }
   // a model with joint equalities runs the generic kernels: no specialisation holds the
   // equality rows' code (engine_impl.h neq_of), and none the rotational contact rows' (condim_of)
-  c.spec = neq > 0 || max_condim > 3 ? 0 : mjx::find_spec(d, dof_parentid.data());
+  // ... and none the elliptic cone's rows and solver (cone_of)
+  c.spec = neq > 0 || max_condim > 3 || cone != 0 ? 0 : mjx::find_spec(d, dof_parentid.data());
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -180,7 +182,7 @@ static mjx::Params host_params(const mjxSim_* s, const Capacity& c, bool max) {
   p.D = s->dd;
   for (int i = 0; i < 3; i++) p.LP[i] = c.lds[i];
   for (int k = 0; k < mjx::kRowClasses; k++) p.LP[3 + k] = max ? c.lds[1] : s->lds_class[k];
-  p.LPJ = mjx::make_lds(c.d, 1, true);
+  p.LPJ = mjx::make_lds(c.d, 1, true, 2, p.o.cone);
   p.nrowclass = max ? 0 : s->nrowclass;
   for (int k = 0; k < mjx::kRowClasses; k++) p.row_cap[k] = s->row_cap[k];
   p.gscr = c.gscr;
@@ -370,9 +372,13 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   dims.nconmax = nconmax;
   dims.njmax = njmax;
   if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                    "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
+                    model->t.o.cone, "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
-  s->nrowclass = mjx::choose_row_classes(s->fast.d, s->fast.spec, s->row_cap);
+  // An elliptic model runs without Newton row classes: a class launch copies the pack's row
+  // slots region by region into its smaller carve, and the grouping words (carve.h make_lds)
+  // are not among them.  Every world then takes the full-capacity carve: the range chain, phase
+  // B, the masked forward and the re-solve, all of which hold the cone solver.
+  s->nrowclass = model->t.o.cone != 0 ? 0 : mjx::choose_row_classes(s->fast.d, s->fast.spec, s->row_cap);
   // batch splits (launch_step): large batches of models without row classes run as
   // concurrent halves.  MJX355_SPLIT=<n> overrides (diagnostic; 1 = one launch set per phase),
   // also for models with row classes (each split then forks its own class streams).
@@ -391,7 +397,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
     dims.nconmax = nconmax_max;
     dims.njmax = njmax_max;
     if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                      "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
+                      model->t.o.cone, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed
     s->ovf_cap = nworld;
@@ -399,7 +405,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   for (int k = 0; k < mjx::kRowClasses; k++) {
     mjx::Dims ds = s->fast.d;
     ds.njmax = k < s->nrowclass ? s->row_cap[k] : s->fast.d.njmax;
-    s->lds_class[k] = mjx::make_lds(ds, 1);
+    s->lds_class[k] = mjx::make_lds(ds, 1, false, 2, model->t.o.cone);
   }
   {
     hipError_t e = hipSuccess;

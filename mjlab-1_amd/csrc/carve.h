@@ -46,9 +46,21 @@ constexpr int ltr_size(int nvp) { return 8 * (nvp >> 2) * ((nvp >> 2) + 1); }
 // torsional / rolling contacts; no other slot depends on it, so every carve of a model without
 // such contacts is what it was)
 constexpr int con_mu_width(int max_condim) { return max_condim > 3 ? 5 : 2; }
-constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false, int mu_w = 2) {
+// cone: the model's friction cone (Opt::cone; 1 = elliptic).  An elliptic carve widens two row
+// slots, each in regions of cone_row_stride(njmax) words, and no other: efc_D becomes [D | group
+// word | scale] -- the hand-off of the contact grouping from phase A to the Newton solver, so it
+// travels in the B pack in front of J (engine_impl.h newton_cone) -- and phase B's efc_jar
+// becomes [jar | kConeScratch regions of per-row solver scratch].  With cone = 0 every carve is
+// byte for byte what it was.
+constexpr int kConeRowWords = 3;  // efc_D regions: D, group word, scale
+constexpr int kConeScratch = 7;   // efc_jar regions behind jar (newton_cone)
+constexpr int cone_row_stride(int njmax) { return (njmax + 3) & ~3; }
+constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false, int mu_w = 2, int cone = 0) {
   Lds L{};
   const int nb = d.nbody, nv = (d.nv + 3) & ~3, C = d.nconmax, R = d.njmax;  // nv padded
+  // (added to the slots' lengths where they are taken, below: the slot table stays what it was)
+  const int extraD = cone ? (kConeRowWords - 1) * cone_row_stride(R) : 0;
+  const int extraJ = cone ? kConeScratch * cone_row_stride(R) : 0;
   constexpr int A = 1, B = 2, Cp = 4;
   // M's slot: phase A factors M in full form; phase B holds M in LTR form and stages the
   // Newton Hessian and its factor in the same form (the MFMA J^T D J variant keeps the full
@@ -112,7 +124,11 @@ constexpr Lds make_lds(const Dims& d, int ph, bool jglobal = false, int mu_w = 2
   auto take = [&](int Lds::*f) {
     if (L.*f != kAbsent) return;
     for (const Slot& sp : all)
-      if (sp.f == f) { L.*f = o; o += (sp.n + 3) & ~3; return; }  // 16-B aligned carve
+      if (sp.f == f) {  // 16-B aligned carve
+        L.*f = o;
+        o += ((sp.n + 3) & ~3) + (f == &Lds::efc_D ? extraD : f == &Lds::efc_jar ? extraJ : 0);
+        return;
+      }
   };
   if (ph == 1) for (auto f : packB) take(f);
   if (ph == 2) {

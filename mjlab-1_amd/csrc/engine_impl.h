@@ -1313,7 +1313,11 @@ __device__ __forceinline__ EqRow eq_row(const DModel& m, const float* eq_data, c
 }
 // con_dim holds the contact's condim, or 0 for a contact in its gap (margin - gap <= dist <
 // margin; mjContact.exclude = 1): it stays in the contact list, has no rows and no force
-__device__ __forceinline__ int con_nrows(int cd) { return cd <= 1 ? cd : 2 * (cd - 1); }
+// Rows: the 2 (cd - 1) pyramid edges, or -- cone != 0, an elliptic model (cone_of) -- the cd
+// basis rows the pyramid combines: normal, two tangents, torsional, two rolling.
+__device__ __forceinline__ int con_nrows(int cd, int cone = 0) {
+  return cd <= 1 ? cd : cone ? cd : 2 * (cd - 1);
+}
 // a contact dimension whose rows phase A does not write (counted as an unsupported pair): any
 // but 0, 1, 3 and -- in a model with such geoms (mcd > 3) -- 4 and 6; model creation refuses
 // them, so this guards a model field rewritten later
@@ -1324,12 +1328,14 @@ __device__ __forceinline__ bool con_dim_unsupported(int cd, int mcd) {
 // model's largest contact dimension (condim_of: the constant 3 in a specialised kernel, whose
 // code is then what it was); a contact keeps con_mu_width(mcd) friction coefficients, and one
 // of dimension 4 / 6 adds its 2 / 6 rotational rows to the normal force.
+// An elliptic contact's rows are the frame's axes: its wrench is the row forces themselves.
 __device__ __forceinline__ V3 con_frame_force(const float* S, const int* Si, const Lds& L, int c,
-                                              int mcd) {
+                                              int mcd, int cone = 0) {
   const int cd = Si[L.con_dim + c];
   if (cd == 0) return V3{0, 0, 0};
   const int r0 = Si[L.con_efc + c];
   if (cd == 1) return V3{S[L.efc_force + r0], 0, 0};
+  if (cone) return V3{S[L.efc_force + r0], S[L.efc_force + r0 + 1], S[L.efc_force + r0 + 2]};
   const int muw = con_mu_width(mcd);
   const float e0 = S[L.efc_force + r0], e1 = S[L.efc_force + r0 + 1];
   const float e2 = S[L.efc_force + r0 + 2], e3 = S[L.efc_force + r0 + 3];
@@ -1340,11 +1346,17 @@ __device__ __forceinline__ V3 con_frame_force(const float* S, const int* Si, con
 }
 // ... and its torque in that frame (torsional about the normal, rolling about the two
 // tangents): component k - 2 = mu_k (f_2k - f_2k+1), zero below dimension 4 (6 for rolling)
-__device__ __forceinline__ V3 con_frame_torque(const float* S, const int* Si, const Lds& L, int c) {
+__device__ __forceinline__ V3 con_frame_torque(const float* S, const int* Si, const Lds& L, int c,
+                                               int cone = 0) {
   const int cd = Si[L.con_dim + c];
   V3 t = {0, 0, 0};
   if (cd <= 3) return t;
   const float* e = S + L.efc_force + Si[L.con_efc + c];
+  if (cone) {  // rows 3 .. 5: about the normal and the two tangents
+    t.x = e[3];
+    if (cd == 6) { t.y = e[4]; t.z = e[5]; }
+    return t;
+  }
   const float* mu = S + L.con_mu + 5 * c;
   t.x = mu[2] * (e[4] - e[5]);
   if (cd == 6) {
@@ -1411,6 +1423,14 @@ template <int SP>
 __device__ __forceinline__ int condim_of(const Params* P) {
   if constexpr (SP > 0) return 3;
   else return P->m.max_condim;
+}
+// The model's friction cone (Opt::cone, 1 = elliptic): pyramidal in every specialisation (an
+// elliptic model is never specialised: capi.cpp make_capacity), so the cone rows of phase A, the
+// cone solver of phase B and the wrench decode of phase C fold away there.  Wave-uniform.
+template <int SP>
+__device__ __forceinline__ int cone_of(const Params* P) {
+  if constexpr (SP > 0) return 0;
+  else return P->o.cone;
 }
 template <int SP, int K>
 __device__ __forceinline__ decltype(auto) lds_of(const Params* P) {
@@ -1948,7 +1968,7 @@ __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* 
                                                      const DModel& m, const Dims& d, float* sd,
                                                      int ncon, int maxmatch, bool all,
                                                      const Params* __restrict__ P, int lane,
-                                                     int mcd) {
+                                                     int mcd, int cone) {
   const int c = lane;
   const bool valid = c < ncon;
   V3 fg = {0, 0, 0}, fc = {0, 0, 0}, tc = {0, 0, 0};  // tc: torque (mcd > 3 only)
@@ -1962,9 +1982,9 @@ __device__ __forceinline__ void contact_sensors_wave(const float* S, const int* 
     m2 = m.geom_csmask1[g2] & m.geom_csmask2[g1];
     if (all) {  // (before the last substep only found counts are computed: no forces)
       dist = S[L.con_dist + c];
-      fc = con_frame_force(S, Si, L, c, mcd);
+      fc = con_frame_force(S, Si, L, c, mcd, cone);
       fg = frame_tv(S + L.con_n + 3 * c, fc);
-      if (mcd > 3) tc = con_frame_torque(S, Si, L, c);
+      if (mcd > 3) tc = con_frame_torque(S, Si, L, c, cone);
     }
   }
   // the sensors' descriptors, lane k = k-th single-slot contact sensor (ncsens <= 64): the
@@ -2086,6 +2106,391 @@ constexpr bool lean_spec() {
 template <int SP> constexpr bool kLean = lean_spec<SP>();
 // (a phase A that evaluates actuator networks holds two more 32-register activation arrays:
 // 2 waves / SIMD, so that they stay out of scratch)
+// --------------------------------------------------------------------------- elliptic cones
+// The Newton solver of an elliptic model ("Elliptic friction cones"; the
+// generic kernels only, under the wave-uniform cone_of).  A contact with friction is one group
+// of dim rows -- normal, two tangents, torsional, two rolling -- whose cost is
+// 1/2 (D_0 / mu^2) dist(U, K)^2 with U = s o jar, N = U_0, T = |U_1..|, K = {N >= mu T}:
+//   top     N >= mu T (or T <= 0, N >= 0): no cost, no force
+//   bottom  mu N + T <= 0 (or T <= 0, N < 0): the rows' quadratics, f_j = -D_j jar_j
+//   middle  1/2 D_m (N - mu T)^2, D_m = D_0 / (mu^2 (1 + mu^2)); with u = U_t / T the Hessian in
+//           jar is D_m [a a' + k (diag(0, s_t^2) - c c')], a = (mu, -mu s_j u_j), c = (0, s_j u_j),
+//           k = mu (mu T - N) / T in (0, 1 + mu^2)
+// Every other row (group word -1) is a one-sided half-quadratic.  The rows' group word (first row
+// | dim << 16) and scale s sit behind D in the elliptic carve's efc_D slot, the solver's per-row
+// scratch behind jar (carve.h make_lds).  A contact's first row's lane evaluates it.
+enum { kConeTop = 0, kConeQuad = 1, kConeMid = 2 };
+__device__ __forceinline__ int cone_zone(float N, float T, float mu) {
+  if (!(T > 0.f)) return N >= 0.f ? kConeTop : kConeQuad;  // (no division by T below)
+  if (N >= mu * T) return kConeTop;
+  if (mu * N + T <= 0.f) return kConeQuad;
+  return kConeMid;
+}
+// A += sum over the nmid middle-zone contacts (first rows mid[]) of J_c' H_c J_c, by the
+// structure above: per tile the combinations a . J_c and c . J_c of the contact's rows
+__device__ __forceinline__ void tiles_add_cone(float (&A)[2][16], const Tiles& T, const float* J,
+                                               const int* grp, const float* ca, const float* cc,
+                                               const float* dh, const float* wa, const float* wc,
+                                               const int* mid, int nmid, int nvp) {
+#pragma unroll
+  for (int s = 0; s < 2; s++) {
+    if (!T.own[s]) continue;
+    const int oi = 4 * T.bi[s], oj = 4 * T.bj[s];
+    for (int k = 0; k < nmid; k++) {
+      const int r0 = mid[k], dim = grp[r0] >> 16;
+      float ai[4] = {0, 0, 0, 0}, aj[4] = {0, 0, 0, 0}, ci[4] = {0, 0, 0, 0}, cj[4] = {0, 0, 0, 0};
+      for (int j = 0; j < dim; j++) {
+        const int r = r0 + j;
+        const float4 a = ld4(J + r * nvp + oi), b = ld4(J + r * nvp + oj);
+        const float ji[4] = {a.x, a.y, a.z, a.w}, jj[4] = {b.x, b.y, b.z, b.w};
+        const float fa = ca[r], fc = cc[r], fd = dh[r];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          ai[q] += fa * ji[q]; aj[q] += fa * jj[q];
+          ci[q] += fc * ji[q]; cj[q] += fc * jj[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+          for (int c = 0; c < 4; c++) A[s][4 * q + c] += fd * ji[q] * jj[c];
+      }
+      const float da = wa[r0], dc = wc[r0];
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int c = 0; c < 4; c++) A[s][4 * q + c] += da * ai[q] * aj[c] + dc * ci[q] * cj[c];
+    }
+  }
+}
+// Returns the iteration count; leaves x, M x, the row forces (efc_force) and qfrc_con in LDS
+// as the pyramidal solver does.  Mt: M in register tiles; Lm: the H / factor staging slot.
+// Every loop is bounded by o.iterations / o.ls_iterations; a non-finite jar fails every zone
+// comparison the same way in every lane, so the loops still end.
+template <int NR, bool LATB>
+__device__ __forceinline__ int newton_cone(float* __restrict__ S, const Lds& L, float* cholbuf,
+                                           const Opt& o, const float* J, int nefc, int nv,
+                                           int nvp, int crs, float (&Mt)[2][16], const Tiles& T,
+                                           int lane) {
+  int* Si = reinterpret_cast<int*>(S);
+  float* jar = S + L.efc_jar;
+  float* Js = S + L.efc_Js;
+  float* wv = S + L.efc_force;
+  const float* Dv = S + L.efc_D;
+  const int* grp = Si + L.efc_D + crs;
+  const float* sv = S + L.efc_D + 2 * crs;
+  int* act = Si + L.efc_act;
+  int* zone = Si + L.efc_jar + crs;
+  float* ca = S + L.efc_jar + 2 * crs;
+  float* cc = S + L.efc_jar + 3 * crs;
+  float* dh = S + L.efc_jar + 4 * crs;
+  float* wa = S + L.efc_jar + 5 * crs;
+  float* wc = S + L.efc_jar + 6 * crs;
+  int* mid = Si + L.efc_jar + 7 * crs;
+  float* Lm = S + L.H;
+  const float scale = 1.0f / (o.meaninertia * (float)max(nv, 1));
+  auto set_jar = [&](const float* xv) {
+    matvec_rows(jar, J, xv, nefc, nvp, lane);
+    for (int r = lane; r < nefc; r += kWave) jar[r] -= S[L.efc_aref + r];
+  };
+  // a contact at jar (+ alpha Js when js is set): N, T and the rows' quadratic sum
+  struct Con { float mu, N, T, quad; int dim, zone; };
+  auto con_at = [&](int r0, int gw) -> Con {
+    Con c;
+    c.dim = gw >> 16;
+    c.mu = sv[r0];
+    c.N = c.mu * jar[r0];
+    c.quad = Dv[r0] * jar[r0] * jar[r0];
+    float tt = 0.f;
+    for (int j = 1; j < c.dim; j++) {
+      const float v = jar[r0 + j], u = sv[r0 + j] * v;
+      tt += u * u;
+      c.quad += Dv[r0 + j] * v * v;
+    }
+    c.T = sqrtf(tt);
+    c.zone = cone_zone(c.N, c.T, c.mu);
+    return c;
+  };
+  // the constraint cost at jar (per lane; the caller sums)
+  auto rows_cost = [&]() -> float {
+    float g = 0.f;
+    for (int r = lane; r < nefc; r += kWave) {
+      const int gw = grp[r];
+      if (gw < 0) {
+        const float v = jar[r];
+        if (v < 0.f) g += 0.5f * Dv[r] * v * v;
+      } else if ((gw & 0xffff) == r) {
+        const Con c = con_at(r, gw);
+        if (c.zone == kConeQuad) {
+          g += 0.5f * c.quad;
+        } else if (c.zone == kConeMid) {
+          const float Dm = Dv[r] / (c.mu * c.mu * (1.f + c.mu * c.mu)), e = c.N - c.mu * c.T;
+          g += 0.5f * Dm * e * e;
+        }
+      }
+    }
+    return g;
+  };
+  auto cost_of = [&](const float* xv, const float* Mxv) -> float {
+    float g = rows_cost();
+    for (int i = lane; i < nv; i += kWave)
+      g += 0.5f * (xv[i] - S[L.qacc_smooth + i]) * (Mxv[i] - S[L.qfrc_smooth + i]);
+    return wave_sum(g);
+  };
+  // zones at jar: per row its zone and wv = -force (D jar; the middle zone's by the rule), and
+  // for a middle contact the Hessian's coefficients.  Then the lists: act = [nquad rows of the
+  // half-quadratics and bottom contacts | the middle contacts' rows], mid = their first rows.
+  // *same: the active rows are those of the previous call (sig).
+  int nquad = 0, nmid = 0;
+  auto classify = [&](unsigned long long (&sig)[4], bool* same) -> int {
+    for (int r = lane; r < nefc; r += kWave) {
+      const int gw = grp[r];
+      if (gw < 0) {
+        const float v = jar[r];
+        zone[r] = v < 0.f ? kConeQuad : kConeTop;
+        wv[r] = v < 0.f ? Dv[r] * v : 0.f;
+      } else if ((gw & 0xffff) == r) {
+        const Con c = con_at(r, gw);
+        if (c.zone != kConeMid) {
+          for (int j = 0; j < c.dim; j++) {
+            zone[r + j] = c.zone;
+            wv[r + j] = c.zone == kConeQuad ? Dv[r + j] * jar[r + j] : 0.f;
+          }
+        } else {
+          const float mu = c.mu, Dm = Dv[r] / (mu * mu * (1.f + mu * mu));
+          const float e = c.N - mu * c.T, iT = 1.f / c.T;
+          const float kap = -mu * e * iT, nf0 = Dm * e * mu;  // nf0 = -f_0 < 0
+          zone[r] = kConeMid;
+          wv[r] = nf0;
+          ca[r] = mu; cc[r] = 0.f; dh[r] = 0.f;
+          wa[r] = Dm; wc[r] = -Dm * kap;
+          for (int j = 1; j < c.dim; j++) {
+            const float sj = sv[r + j], su = sj * sj * jar[r + j] * iT;  // s_j u_j
+            zone[r + j] = kConeMid;
+            wv[r + j] = -nf0 * su;
+            ca[r + j] = -mu * su;
+            cc[r + j] = su;
+            dh[r + j] = Dm * kap * sj * sj;
+          }
+        }
+      }
+    }
+    sync();
+    int nq = 0, nm = 0, nl = 0;
+    bool eq = nefc <= 4 * kWave;
+    for (int r0 = 0, k = 0; r0 < nefc; r0 += kWave, k++) {
+      const int r = r0 + lane;
+      const int z = r < nefc ? zone[r] : kConeTop;
+      const unsigned long long bq = __ballot(z == kConeQuad);
+      if (z == kConeQuad) act[nq + __popcll(bq & ((1ull << lane) - 1ull))] = r;
+      nq += __popcll(bq);
+      const unsigned long long ba = __ballot(z != kConeTop);
+      if (k < 4) { eq = eq && ba == sig[k]; sig[k] = ba; }
+    }
+    for (int r0 = 0; r0 < nefc; r0 += kWave) {
+      const int r = r0 + lane;
+      const bool fm = r < nefc && zone[r] == kConeMid;
+      const unsigned long long bm = __ballot(fm);
+      if (fm) act[nq + nm + __popcll(bm & ((1ull << lane) - 1ull))] = r;
+      nm += __popcll(bm);
+      const bool fl = fm && (grp[r] & 0xffff) == r;
+      const unsigned long long bl = __ballot(fl);
+      if (fl) mid[nl + __popcll(bl & ((1ull << lane) - 1ull))] = r;
+      nl += __popcll(bl);
+    }
+    sync();
+    *same = eq;
+    nquad = nq;
+    nmid = nl;
+    return nq + nm;
+  };
+  // warmstart: keep qacc_warmstart if its cost beats qacc_smooth
+  for (int i = lane; i < nvp; i += kWave) S[L.x + i] = S[L.qacc_ws + i];
+  sync();
+  tiles_symv(Mt, T, S + L.x, S + L.Mx, nvp, lane);
+  set_jar(S + L.x);
+  sync();
+  const float cost_ws = cost_of(S + L.x, S + L.Mx);
+  sync();
+  set_jar(S + L.qacc_smooth);
+  sync();
+  const float cost_sm = cost_of(S + L.qacc_smooth, S + L.qfrc_smooth);
+  sync();
+  float cost;
+  if (cost_sm < cost_ws) {
+    for (int i = lane; i < nvp; i += kWave) {
+      S[L.x + i] = S[L.qacc_smooth + i];
+      S[L.Mx + i] = S[L.qfrc_smooth + i];
+    }
+    cost = cost_sm;
+  } else {
+    set_jar(S + L.x);
+    cost = cost_ws;
+  }
+  sync();
+  int niter = 0;
+  unsigned long long act_sig[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+  bool mid_factor = false;  // the stored factor holds a middle-zone Hessian
+  for (int iter = 0; iter < o.iterations; iter++) {
+    bool same_set;
+    const int nact = classify(act_sig, &same_set);
+    // H depends on jar in the middle zone: the stored factor only with the active rows
+    // unchanged and no contact there, now or when it was made (a contact that went from the
+    // middle to the bottom zone keeps its rows active and changes H)
+    const bool refactor = iter == 0 || !same_set || nmid > 0 || mid_factor;
+    if (refactor) mid_factor = nmid > 0;
+    jt_mul(S + L.srch, J, wv, act, nact, nvp, lane);
+    float gn = 0.f, gr = 0.f;
+    if (lane < nvp) {
+      const float jf = S[L.srch + lane], mx = S[L.Mx + lane], fs = S[L.qfrc_smooth + lane];
+      const float g = jf + mx - fs;
+      S[L.srch + lane] = -g;
+      gn += g * g;
+      const float a = fabsf(jf) + fabsf(mx) + fabsf(fs);
+      gr += a * a;
+    }
+    gn = sqrtf(wave_sum(gn));
+    gr = sqrtf(wave_sum(gr));
+    if (iter > 0 && scale * gn < fmaxf(o.tolerance, 16.f * FLT_EPSILON * scale * gr)) break;
+    if (refactor) {
+      float A[2][16];
+#pragma unroll
+      for (int s2 = 0; s2 < 2; s2++)
+#pragma unroll
+        for (int e2 = 0; e2 < 16; e2++) A[s2][e2] = Mt[s2][e2];
+      tiles_add_jtdj(A, T, J, Dv, act, nquad, nvp);
+      tiles_add_cone(A, T, J, grp, ca, cc, dh, wa, wc, mid, nmid, nvp);
+      tiles_store_ltr(A, T, Lm);
+    }
+    sync();
+    {
+      float R[NR];
+      float rd;
+      if (refactor) {
+        rows_load_ltr<NR>(R, Lm, nvp, lane);
+        rows_chol<NR, LATB>(R, rd, cholbuf, nvp, lane);
+        rows_store_strict_ltr<NR>(R, rd, Lm, nvp, lane);
+        rows_fwd_rows<NR>(R, rd, lane);
+      } else {
+        rows_load_factor_ltr<NR>(R, rd, Lm, nvp, lane);
+      }
+      sync();
+      float xs = lane < nvp ? S[L.srch + lane] : 0.f;
+      xs = rows_solve_ltr<NR>(R, rd, Lm, xs, nvp, lane);
+      sync();
+      if (lane < nvp) S[L.srch + lane] = xs;
+      sync();
+    }
+    matvec_rows(Js, J, S + L.srch, nefc, nvp, lane);
+    tiles_symv(Mt, T, S + L.srch, S + L.Ms, nvp, lane);
+    float g1 = 0.f, sn = 0.f, sdir = 0.f;
+    if (lane < nv) {
+      sdir = S[L.srch + lane];
+      g1 += sdir * (S[L.Mx + lane] - S[L.qfrc_smooth + lane]);
+      sn += sdir * sdir;
+    }
+    sync();
+    float g2 = 0.f;
+    if (lane < nv) g2 += sdir * S[L.Ms + lane];
+    g1 = wave_sum(g1);
+    g2 = wave_sum(g2);
+    sn = sqrtf(wave_sum(sn));
+    const float gtol = o.tolerance * o.ls_tolerance * sn / scale;
+    // exact line search on the C1 convex cost: first and second derivative along the step by
+    // zone at alpha; `noise`: the fp32 rounding floor of the derivative's summed terms (the
+    // middle zone's N - mu T cancels, so its terms count |N| + mu T)
+    auto ls_eval = [&](float alpha, float* der, float* der2, float* noise) {
+      float f1 = 0.f, f2 = 0.f, fa = 0.f;
+      for (int r = lane; r < nefc; r += kWave) {
+        const int gw = grp[r];
+        if (gw < 0) {
+          const float js = Js[r], v = jar[r] + alpha * js;
+          // (at alpha = 0 a row on its boundary counts when the step enters it: the one-sided
+          // second derivative at 0+)
+          if (v < 0.f || (alpha == 0.f && v == 0.f && js < 0.f)) {
+            const float t = Dv[r] * v * js;
+            f1 += t;
+            fa += fabsf(t);
+            f2 += Dv[r] * js * js;
+          }
+        } else if ((gw & 0xffff) == r) {
+          const int dim = gw >> 16;
+          const float mu = sv[r], js0 = Js[r], x0 = jar[r] + alpha * js0;
+          const float N = mu * x0, V0 = mu * js0;
+          float q1 = Dv[r] * x0 * js0, qa = fabsf(q1), q2 = Dv[r] * js0 * js0;
+          float tt = 0.f, uv = 0.f, vv = 0.f;
+          for (int j = 1; j < dim; j++) {
+            const float js = Js[r + j], x = jar[r + j] + alpha * js, sj = sv[r + j];
+            const float u = sj * x, v = sj * js, t = Dv[r + j] * x * js;
+            tt += u * u; uv += u * v; vv += v * v;
+            q1 += t; qa += fabsf(t); q2 += Dv[r + j] * js * js;
+          }
+          const float Tn = sqrtf(tt);
+          const int z = cone_zone(N, Tn, mu);
+          if (z == kConeQuad) {
+            f1 += q1; fa += qa; f2 += q2;
+          } else if (z == kConeMid) {
+            const float Dm = Dv[r] / (mu * mu * (1.f + mu * mu));
+            const float e = N - mu * Tn, p = uv / Tn, dd = V0 - mu * p;
+            f1 += Dm * e * dd;
+            fa += Dm * (fabsf(N) + mu * Tn) * (fabsf(V0) + mu * fabsf(p));
+            f2 += Dm * (dd * dd + (-mu * e / Tn) * fmaxf(vv - p * p, 0.f));
+          }
+        }
+      }
+      f1 = wave_sum(f1);
+      f2 = wave_sum(f2);
+      fa = wave_sum(fa);
+      *der = g1 + alpha * g2 + f1;
+      *der2 = g2 + f2;
+      *noise = 64.f * FLT_EPSILON * (fabsf(g1) + fabsf(alpha * g2) + fa);
+    };
+    float d0, c0, nz0;
+    ls_eval(0.f, &d0, &c0, &nz0);  // c0: the curvature at 0+
+    float alpha = 0.f;
+    if (d0 < 0) {
+      float lo = 0.f, hi = -1.f, best = 0.f;
+      float a = c0 > 0 ? -d0 / c0 : 1.f;
+      bool done = false;
+      for (int it = 0; it < o.ls_iterations; it++) {
+        float der, der2, nz;
+        ls_eval(a, &der, &der2, &nz);
+        if (fabsf(der) <= fmaxf(gtol, nz)) { alpha = a; done = true; break; }
+        if (der < 0) { lo = a; best = a; } else { hi = a; }
+        float next = der2 > 0 ? a - der / der2 : a * 2;
+        if (hi >= 0 && !(next > lo && next < hi)) next = 0.5f * (lo + hi);
+        if (hi < 0 && next <= lo) next = lo + (lo > 0 ? lo : 1.0f);
+        a = next;
+      }
+      if (!done) alpha = best > 0 ? best : a;
+    }
+    niter = iter + 1;
+    if (!(alpha > 0.f)) break;  // (a non-finite step ends the solve as a zero one does)
+    if (lane < nvp) {
+      S[L.x + lane] += alpha * S[L.srch + lane];
+      S[L.Mx + lane] += alpha * S[L.Ms + lane];
+    }
+    for (int r = lane; r < nefc; r += kWave) jar[r] += alpha * Js[r];
+    sync();
+    const float old = cost;
+    cost = cost_of(S + L.x, S + L.Mx);
+    // MuJoCo's improvement test.  No fp32 floor on the cost here: in the middle zone the solve
+    // closes in gradually, and a residual gradient whose descent is below the cost's fp32
+    // resolution (eps |cost|, mostly the Gauss term) still moves qfrc_constraint by many times
+    // its rounding.  The line search works on the derivative, which resolves that progress; the
+    // solve ends on the gradient test above, on a zero step, or when the cost stops decreasing.
+    if (!(scale * (old - cost) >= o.tolerance)) break;
+  }
+  // the row forces by zone and qfrc_constraint = J' f over the active rows
+  sync();
+  unsigned long long sig_f[4] = {0, 0, 0, 0};
+  bool same_f;
+  const int nact = classify(sig_f, &same_f);
+  for (int r = lane; r < nefc; r += kWave) wv[r] = -wv[r];
+  sync();
+  jt_mul(S + L.qfrc_con, J, wv, act, nact, nvp, lane);
+  return niter;
+}
+
 #define MJX_PHASE_ATTR __attribute__((amdgpu_waves_per_eu(NET && PH == 0 ? (NR <= 48 ? 2 : 1) : PH == 1 && kLean<SP> ? 4 : (PH == 1 || PH == 0) && NR <= 48 ? 3 : 1)))
 #define MJX_PHASE_ATTR_B __attribute__((amdgpu_waves_per_eu(NR <= 48 ? 3 : 1)))
 // One world through phase PH (0 = A, 1 = B, 2 = C) in the wave's LDS S: the
@@ -2116,6 +2521,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
   // in a specialised kernel)
   const int mcd = condim_of<SP>(P);
   const int muw = con_mu_width(mcd);
+  // the friction cone (the constant 0 in a specialised kernel); crs: the stride of the row
+  // regions an elliptic carve adds (carve.h make_lds)
+  const int cone = cone_of<SP>(P);
+  const int crs = cone_row_stride(d.njmax);
+  (void)crs;
   // phase B: `integrate` carries the Newton row class (0 = full capacity, k > 0 = LP[2 + k])
   constexpr bool JG = PH == 1 && (LAT & 2) != 0;
   constexpr bool NET = PH == 0 && (LAT & 4) != 0;
@@ -3185,21 +3595,21 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       int cdim = 0, crow = 0, con_total = 0, con_off = 0;
       if (con1) {
         cdim = lane < ncon ? Si[L.con_dim + lane] : 0;
-        crow = lane < ncon ? con_nrows(cdim) : 0;
+        crow = lane < ncon ? con_nrows(cdim, cone) : 0;
         if (lane < ncon && con_dim_unsupported(cdim, mcd)) atomicOr(&ints[3], 4);
         con_off = wave_excl_scan(crow, lane, &con_total);
       } else {
         for (int c0 = 0; c0 < ncon; c0 += kWave) {
           const int c = c0 + lane;
           const int cd = c < ncon ? Si[L.con_dim + c] : 0;
-          const int cr = c < ncon ? con_nrows(cd) : 0;
+          const int cr = c < ncon ? con_nrows(cd, cone) : 0;
           if (c < ncon && con_dim_unsupported(cd, mcd)) atomicOr(&ints[3], 4);
           int tot, off = wave_excl_scan(cr, lane, &tot);
           if (c < ncon) Si[L.con_efc + c] = con_total + off;
           con_total += tot;
         }
       }
-      auto con_rows = [&](int c) { return con_nrows(Si[L.con_dim + c]); };
+      auto con_rows = [&](int c) { return con_nrows(Si[L.con_dim + c], cone); };
       int nefc = lim_total + con_total;
       if (P->ovf_resolve) {
         // contacts or rows past this carve: list the world for the re-solve at full capacity
@@ -3319,6 +3729,22 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         float jn = dot(F.n, jd);
         if (dim == 1) {
           Jg[r0 * nvp + i] = jn;
+        } else if (cone && dim != 0) {
+          // elliptic: the basis rows themselves (normal, tangents, then the relative angular
+          // velocity about the normal and the tangents)
+          Jg[(r0 + 0) * nvp + i] = jn;
+          Jg[(r0 + 1) * nvp + i] = dot(F.t, jd);
+          Jg[(r0 + 2) * nvp + i] = dot(F.b, jd);
+          if (dim > 3) {
+            V3 wd = {0, 0, 0};
+            if (in2) wd = wd + cang;
+            if (in1) wd = wd - cang;
+            Jg[(r0 + 3) * nvp + i] = dot(F.n, wd);
+            if (dim == 6) {
+              Jg[(r0 + 4) * nvp + i] = dot(F.t, wd);
+              Jg[(r0 + 5) * nvp + i] = dot(F.b, wd);
+            }
+          }
         } else if (dim != 0) {
           float jt1 = dot(F.t, jd);
           float jt2 = dot(F.b, jd);
@@ -3473,6 +3899,34 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           B = S[L.con_kb + 2 * c + 1];
         }
         float Rr = fmaxf(MINVAL, (1 - imp) * diag / imp);
+        // Elliptic contact row j (EFC_PYRAMIDAL codes the rows of any contact with friction):
+        // R_0 from the normal row's diagApprox, R_1 = R_0 / impratio, R_j = R_1 f0^2 /
+        // friction[j-1]^2; the friction rows have no position term; the group word (first row
+        // | dim << 16) and the scale s_j (row 0: the cone coefficient f0 / sqrt(impratio)) go
+        // to phase B behind D.  Every other row of such a model is ordinary: group word -1.
+        const bool erow = cone && type == EFC_PYRAMIDAL;
+        int ej = 0;
+        if (cone) {
+          int gword = -1;
+          float sc = 0.f;
+          if (erow) {
+            const int c = pl, r0 = Si[L.con_efc + c];
+            ej = r - r0;
+            const int cb = Si[L.con_key + c];
+            const float tran = binvw[2 * cb_b1(cb)] + binvw[2 * cb_b2(cb)];
+            const float f0 = S[L.con_mu + muw * c];
+            Rr = fmaxf(MINVAL, (1 - imp) / imp * tran);
+            sc = f0 / sqrtf(o.impratio);
+            if (ej > 0) {
+              const float fj = S[L.con_mu + muw * c + ej - 1];
+              Rr = Rr / o.impratio * (f0 * f0) / (fj * fj);
+              sc = fj;
+            }
+            gword = r0 | Si[L.con_dim + c] << 16;
+          }
+          Si[L.efc_D + crs + r] = gword;
+          S[L.efc_D + 2 * crs + r] = sc;
+        }
         // efc_vel = J qvel, evaluated from the body velocities (cvel is the same chain sum)
         float vel;
         if (neq > 0 && type == EFC_EQUALITY) {
@@ -3487,7 +3941,17 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           V3 v = point_vel_r(S, L, cb_b2(cb), cb_r2(cb), pc) - point_vel_r(S, L, cb_b1(cb), cb_r1(cb), pc);
           const CFrame F = cframe(v3(S + L.con_n + 3 * c));
           vel = dot(F.n, v);
-          if (type != EFC_FRICTIONLESS) {
+          if (erow) {
+            if (ej >= 3) {
+              const int b1 = cb_b1(cb), b2 = cb_b2(cb);
+              V3 wr = {0, 0, 0};
+              if (b2 > 0) wr = wr + v3(S + L.cvel + 6 * b2);
+              if (b1 > 0) wr = wr - v3(S + L.cvel + 6 * b1);
+              vel = dot(ej == 3 ? F.n : ej == 4 ? F.t : F.b, wr);
+            } else if (ej > 0) {
+              vel = dot(ej == 1 ? F.t : F.b, v);
+            }
+          } else if (type != EFC_FRICTIONLESS) {
             int kr = r - Si[L.con_efc + c];
             float mu = S[L.con_mu + muw * c + (kr >> 1)];
             if (mcd > 3 && kr >= 4) {
@@ -3505,7 +3969,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           }
         }
         S[L.efc_D + r] = 1.0f / Rr;
-        S[L.efc_aref + r] = -B * vel - K * imp * (pos - margin);
+        S[L.efc_aref + r] = erow && ej > 0 ? -B * vel : -B * vel - K * imp * (pos - margin);
       }
       if (lane == 0) { ints[1] = nefc; ints[2] = lim_total - eq_total; ints[4] = ncon; ints[6] = dense_h; }
       sync();
@@ -3575,7 +4039,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          const V3 f = con_frame_force(S, Si, L, c, mcd);
+          const V3 f = con_frame_force(S, Si, L, c, mcd, cone);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -3601,10 +4065,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              const V3 f = con_frame_force(S, Si, L, c, mcd);
+              const V3 f = con_frame_force(S, Si, L, c, mcd, cone);
               oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
             } else if (mcd > 3 && (bits & 4)) {
-              const V3 t = con_frame_torque(S, Si, L, c);
+              const V3 t = con_frame_torque(S, Si, L, c, cone);
               oo[0] = t.x; oo[1] = t.y; oo[2] = t.z;
             }
           }
@@ -3689,6 +4153,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     cp4(gw + LB.ints, S + L.ints, 8, lane);  // (qacc_smooth, qfrc_smooth: stored above)
     cp4(gw + LB.efc_aref, S + L.efc_aref, nr4, lane);
     cp4(gw + LB.efc_D, S + L.efc_D, nr4, lane);
+    if (cone) {  // the grouping words and scales (carve.h make_lds)
+      cp4(gw + LB.efc_D + crs, S + L.efc_D + crs, nr4, lane);
+      cp4(gw + LB.efc_D + 2 * crs, S + L.efc_D + 2 * crs, nr4, lane);
+    }
     // (the C pack's last-substep part only in the last substep: carve.h packC)
     if (obs) {
       cp4(gc + LC.cdof, S + L.cdof, 6 * nvp, lane);
@@ -3760,6 +4228,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         S[L.qfrc_con + i] = 0.f;
       }
       sync();
+    } else if (cone != 0) {
+      // an elliptic model: the cone-aware solver (never the register-row path below)
+      if constexpr (SP == 0)
+        niter = newton_cone<NR, (LAT & 1) != 0>(S, L, S + LB.chol, o, JG ? gw + LB.efc_J : S + L.efc_J,
+                                                 nefc, nv, nvp, crs, Mt, T, lane);
     } else {
       float* jar = S + L.efc_jar;
       float* Js = S + L.efc_Js;
@@ -4215,7 +4688,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
           if (found >= o.maxmatch) continue;  // contact_sensor_maxmatch: the first matches only
           found++;
           // contact force in contact frame
-          const V3 f = con_frame_force(S, Si, L, c, mcd);
+          const V3 f = con_frame_force(S, Si, L, c, mcd, cone);
           V3 fg = frame_tv(S + L.con_n + 3 * c, f);
           net = net + fg * (a1 ? 1.f : -1.f);
           float k = reduce == REDUCE_MINDIST ? S[L.con_dist + c]
@@ -4241,10 +4714,10 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
             else if (bits & 32) { for (int t = 0; t < 3; t++) oo[t] = sg * S[L.con_n + 3 * c + t]; }
             else if (bits & 64) { for (int t = 0; t < 3; t++) oo[t] = sg * vc(cframe(v3(S + L.con_n + 3 * c)).t, t); }
             else if (bits & 2) {
-              const V3 f = con_frame_force(S, Si, L, c, mcd);
+              const V3 f = con_frame_force(S, Si, L, c, mcd, cone);
               oo[0] = f.x; oo[1] = f.y; oo[2] = f.z;
             } else if (mcd > 3 && (bits & 4)) {
-              const V3 t = con_frame_torque(S, Si, L, c);
+              const V3 t = con_frame_torque(S, Si, L, c, cone);
               oo[0] = t.x; oo[1] = t.y; oo[2] = t.z;
             }
           }
@@ -4253,7 +4726,7 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
     }
     if (kCon1<SP> || ncon <= kWave)
       contact_sensors_wave(S, Si, L, m, d, D.sensordata + (size_t)w * d.nsensordata, ncon,
-                           o.maxmatch, last || P->outputs_every, P, lane, mcd);
+                           o.maxmatch, last || P->outputs_every, P, lane, mcd, cone);
     st.stamp(11);
     if (last) {
       size_t wb = (size_t)w * nb;
@@ -4262,13 +4735,13 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
       const int nout = min(P->con_stride, D.wstats[8 * (size_t)w + 6]);  // phase A's output slots
       for (int c = lane; c < nout; c += kWave) {
         V3 f = {0, 0, 0};
-        if (c < ncon && nefc > 0) f = con_frame_force(S, Si, L, c, mcd);
+        if (c < ncon && nefc > 0) f = con_frame_force(S, Si, L, c, mcd, cone);
         D.contact_force[(wc + c) * 3] = f.x;
         D.contact_force[(wc + c) * 3 + 1] = f.y;
         D.contact_force[(wc + c) * 3 + 2] = f.z;
         if (mcd > 3) {
           V3 t = {0, 0, 0};
-          if (c < ncon && nefc > 0) t = con_frame_torque(S, Si, L, c);
+          if (c < ncon && nefc > 0) t = con_frame_torque(S, Si, L, c, cone);
           float* ct = m.contact_torque + (wc + c) * 3;
           ct[0] = t.x; ct[1] = t.y; ct[2] = t.z;
         }

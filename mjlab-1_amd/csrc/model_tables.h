@@ -77,7 +77,8 @@ inline std::string check_limits(const mjxModelDesc& desc) {
   }
   if (desc.nu > kMaxLanes || desc.njnt > kMaxLanes)
     return "at most 64 actuators and 64 joints per world supported";
-  if (desc.cone != 0) return "only pyramidal cones are supported";
+  if (desc.cone != 0 && desc.cone != 1)
+    return "cone " + std::to_string(desc.cone) + " is not supported (0 pyramidal, 1 elliptic)";
   if (desc.contact_maxmatch < 1) return "contact_maxmatch must be >= 1";
   return "";
 }

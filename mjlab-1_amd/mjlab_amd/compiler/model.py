@@ -78,6 +78,8 @@ REFUSED_SENSORS = {
   "e_potential": "the engine does not compute energies",
   "e_kinetic": "the engine does not compute energies"}
 SUPPORTED_CONDIM = (1, 3, 4, 6)
+# friction cones (Model.cone): an elliptic contact of dimension dim has dim rows, not 2 (dim - 1)
+CONES = {"pyramidal": 0, "elliptic": 1}
 CONTACT_FIELD_DIM = {"found": 1, "force": 3, "torque": 3, "dist": 1, "pos": 3, "normal": 3,
                      "tangent": 3}
 CONTACT_FIELD_BIT = {"found": 0, "force": 1, "torque": 2, "dist": 3, "pos": 4, "normal": 5,
@@ -238,7 +240,7 @@ class Model:
   ls_tolerance: float = 0.01
   impratio: float = 1.0
   integrator: int = 1      # 0 euler, 1 implicitfast
-  cone: int = 0            # 0 pyramidal, 1 elliptic (unsupported)
+  cone: int = 0            # 0 pyramidal, 1 elliptic (CONES)
   contact_maxmatch: int = 64  # SimulationCfg.contact_sensor_maxmatch (sim/sim.py:95,141)
   solver: int = 2          # 2 newton
   meaninertia: float = 1.0
@@ -424,8 +426,8 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   (terrain_geoms: the TerrainGenerator's HFieldSpec / BoxSpec geoms in generation order,
   on the static `terrain` body, `terrains/terrain_generator.py:93-114`), "hfield" (the
   same with heightfields only) or "none"."""
-  if cone != "pyramidal":
-    raise NotImplementedError("only pyramidal friction cones are supported")
+  if cone not in CONES:
+    raise ValueError(f"cone {cone!r}: 'pyramidal' or 'elliptic'")
   B = _Builder()
   B.add_body("world", -1, np.zeros(3), np.array([1.0, 0, 0, 0]), None)
   geoms, sites, joints = [], [], []
@@ -1016,6 +1018,7 @@ def compile_scene(entities: list[EntitySpec], *, terrain: str = "plane",
   m.timestep, m.iterations, m.ls_iterations = timestep, iterations, ls_iterations
   m.tolerance, m.ls_tolerance, m.impratio = tolerance, ls_tolerance, impratio
   m.integrator = {"euler": 0, "implicitfast": 1}[integrator]
+  m.cone = CONES[cone]
   m.gravity = np.asarray(gravity, float)
 
   # tree helpers for the HIP engine (level lists, children lists, dof->body masks)

@@ -186,6 +186,8 @@ def ensure_library(model, nconmax: int, njmax: int, role: int, compile_ok: bool 
   cd = np.asarray(model.arrays.get("geom_condim", ())).reshape(-1)
   if cd.size and int(cd.max()) > 3:
     return None
+  if int(getattr(model, "cone", 0)) != 0:  # likewise the elliptic cone's rows and solver
+    return None
   path, text, sid = library_path(model, nconmax, njmax, role)
   hit = _lookup(path)
   if hit is not None:

@@ -24,6 +24,7 @@ from .._lib import MjxError, check, lib
 from .sim_data import DeviceBridge, field_tensor
 
 _INTEGRATORS = {"euler": 0, "implicitfast": 1}
+_CONES = {"pyramidal": 0, "elliptic": 1}  # Model.cone (an elliptic model: the generic kernels only)
 
 
 @dataclass
@@ -45,12 +46,12 @@ class MujocoCfg:
 
   def apply(self, model) -> None:
     """Apply configuration settings to a compiled model (MujocoCfg.apply)."""
-    if self.cone != "pyramidal":
-      raise NotImplementedError("only pyramidal friction cones are implemented")
+    if self.cone not in _CONES:
+      raise ValueError(f"cone {self.cone!r}: 'pyramidal' or 'elliptic'")
     if self.solver != "newton":
       raise NotImplementedError("only the Newton solver is implemented")
     model.integrator = _INTEGRATORS[self.integrator]
-    model.cone = 0
+    model.cone = _CONES[self.cone]
     model.timestep = float(self.timestep)
     model.impratio = float(self.impratio)
     model.gravity = np.asarray(self.gravity, dtype=np.float64)
@@ -220,7 +221,9 @@ def _max_condim(model) -> int:
 
 def _contact_rows(model) -> int:
   """Rows the capacities count per contact: the four of a sliding contact, or the
-  2 (max_condim - 1) of the model's largest torsional / rolling one (6 or 10)."""
+  2 (max_condim - 1) of the model's largest torsional / rolling one (6 or 10).  An elliptic
+  contact has `dim` rows, and 2 (dim - 1) >= dim for dim >= 2: the same numbers bound an
+  elliptic model's rows, so its capacities, warning and refusals are the pyramidal ones."""
   mcd = _max_condim(model)
   return 2 * (mcd - 1) if mcd > 3 else 4
 
@@ -331,6 +334,10 @@ class Simulation:
       raise NotImplementedError(
           "specialize='always': a model with torsional or rolling contacts (condim 4 or 6) runs "
           "the generic kernels only (their rows are not compiled into specialised or JIT kernels)")
+    if cfg.specialize == "always" and int(getattr(model, "cone", 0)) != 0:
+      raise NotImplementedError(
+          "specialize='always': a model with elliptic friction cones runs the generic kernels "
+          "only (the cone rows and solver are not compiled into specialised or JIT kernels)")
     dev = torch.device(device)
     if dev.type != "cuda":
       raise MjxError("mjlab_amd.Simulation runs only on a ROCm GPU (device 'cuda:N'); "
@@ -610,8 +617,9 @@ class Simulation:
     env = os.environ.get("MJX355_JIT")
     if env is not None:
       policy = "always" if env != "0" else "never"
-    if _max_condim(model) > 3:
-      # likewise the rotational contact rows (csrc/engine_impl.h condim_of)
+    if _max_condim(model) > 3 or int(getattr(model, "cone", 0)) != 0:
+      # likewise the rotational contact rows (csrc/engine_impl.h condim_of) and the elliptic
+      # cone's rows and solver (cone_of)
       return False
     if _neq(model) > 0:
       # equality rows exist only in the generic kernels (csrc/engine_impl.h neq_of): a
