@@ -93,7 +93,7 @@ struct Capacity {
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
 static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid, int neq,
-                         int max_condim, int cone, const char* too_big, Capacity& c) {
+                         int max_condim, int cone, int ncylinder, const char* too_big, Capacity& c) {
   c.d = d;
   for (int i = 0; i < 3; i++) {
     // (phases A and C hold the contacts' friction coefficients: five each with torsional or
@@ -104,8 +104,9 @@ static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_par
   }
   // a model with joint equalities runs the generic kernels: no specialisation holds the
   // equality rows' code (engine_impl.h neq_of), and none the rotational contact rows' (condim_of)
-  // ... and none the elliptic cone's rows and solver (cone_of)
-  c.spec = neq > 0 || max_condim > 3 || cone != 0 ? 0 : mjx::find_spec(d, dof_parentid.data());
+  // ... and none the elliptic cone's rows and solver (cone_of).  The cylinder narrowphase is in
+  // the run-time specialisations compiled for a model with cylinder pairs only (kCylinder)
+  c.spec = neq > 0 || max_condim > 3 || cone != 0 ? 0 : mjx::find_spec(d, dof_parentid.data(), ncylinder);
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -372,7 +373,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   dims.nconmax = nconmax;
   dims.njmax = njmax;
   if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                    model->t.o.cone, "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
+                    model->t.o.cone, model->t.ncylinder, "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
   // An elliptic model runs without Newton row classes: a class launch copies the pack's row
   // slots region by region into its smaller carve, and the grouping words (carve.h make_lds)
@@ -397,7 +398,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
     dims.nconmax = nconmax_max;
     dims.njmax = njmax_max;
     if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                      model->t.o.cone, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
+                      model->t.o.cone, model->t.ncylinder, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed
     s->ovf_cap = nworld;
@@ -909,7 +910,9 @@ int mjx_spec_register(const char* path) {
   int par[64];
   const int n = tree(par, 64);
   if (n < 0 || n > 64) return fail("bad dof tree in the jit library");
-  return mjx::register_spec(d, par, n, kern);  // the library stays loaded for the process
+  // (optional entry point: a library without it holds no cylinder narrowphase)
+  auto ncyl = reinterpret_cast<AbiFn>(dlsym(h, "mjx_jit_ncyl"));
+  return mjx::register_spec(d, par, n, kern, ncyl ? ncyl() : 0);  // the library stays loaded for the process
 }
 
 int mjx_sim_mass_matrix(mjxSim* s, int big, float* out, void* stream) {

@@ -28,7 +28,8 @@ constexpr int kStaticChunk = 64; // terrain geoms per broadphase chunk
 
 enum { EFC_LIMIT = 0, EFC_FRICTIONLESS = 1, EFC_PYRAMIDAL = 2, EFC_EQUALITY = 3 };
 constexpr int kMaxEq = 64;       // equalities per world: one lane each in phase A's row count
-enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_BOX = 6 };
+enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_CYLINDER = 5,
+       GEOM_BOX = 6 };
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
 enum { SENS_GYRO = 0, SENS_VELOCIMETER = 1, SENS_ACCELEROMETER = 2, SENS_SUBTREEANGMOM = 3,
        SENS_CONTACT = 4, SENS_FRAMEPOS = 5, SENS_FRAMEQUAT = 6, SENS_JOINTPOS = 7,
@@ -180,12 +181,12 @@ namespace mjx {
 // compile-time constants).  find_spec returns the entry equal to d in every field and in
 // the dof tree (dof_parentid, for the tree-form SPD factors), else 0.
 constexpr int kMaxSpecs = 8;
-int find_spec(const Dims& d, const int* dof_parentid);
+int find_spec(const Dims& d, const int* dof_parentid, int ncylinder = 0);
 // Specialisations compiled at run time (jit.hip, loaded by mjx_spec_register) get ids from
 // kRtSpecBase on; find_spec checks them after the compiled specs.inc entries.
 constexpr int kRtSpecBase = 1000;
 using StepFnPtr = void (*)(const struct Params*, int, int, int, int, int, const uint8_t*);
-int register_spec(const Dims& d, const int* par, int npar, StepFnPtr (*fn)(int));
+int register_spec(const Dims& d, const int* par, int npar, StepFnPtr (*fn)(int), int ncylinder = 0);
 
 // Explicit actuators (include/mjx355.h mjxActuatorDesc): per-actuator kinds and lag ranges,
 // and the torch-owned per-world buffers, each [nworld, nu] but the ring.

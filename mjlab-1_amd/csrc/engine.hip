@@ -163,13 +163,14 @@ struct RtSpec {
   Dims d;
   std::vector<int> par;
   StepFn (*fn)(int);
+  int ncyl;  // cylinder pairs its kernels were compiled for (engine_impl.h SpecCyl)
 };
 static std::vector<RtSpec>& rt_specs() {
   static std::vector<RtSpec> v;
   return v;
 }
-int register_spec(const Dims& d, const int* par, int npar, StepFn (*fn)(int)) {
-  rt_specs().push_back(RtSpec{d, std::vector<int>(par, par + npar), fn});
+int register_spec(const Dims& d, const int* par, int npar, StepFn (*fn)(int), int ncylinder) {
+  rt_specs().push_back(RtSpec{d, std::vector<int>(par, par + npar), fn, ncylinder});
   return kRtSpecBase + (int)rt_specs().size() - 1;
 }
 static StepFn spec_fn(int spec, int ph) {
@@ -243,7 +244,7 @@ static void launch(const Worlds& W, PhaseCode code, int cls, bool with_next_a, h
              arg, W.mask);
 }
 
-int find_spec(const Dims& d, const int* dof_parentid) {
+int find_spec(const Dims& d, const int* dof_parentid, int ncylinder) {
   if (const char* e = getenv("MJX355_NO_SPEC"))  // diagnostic: force the generic kernels
     if (atoi(e) != 0) return 0;
   auto eq = [](const Dims& a, const Dims& b) {
@@ -262,13 +263,16 @@ int find_spec(const Dims& d, const int* dof_parentid) {
       if (dof_parentid[i] != par[i]) return false;
     return true;
   };
+  // (a model with cylinder pairs takes only kernels compiled with their narrowphase)
 #define MJX_SPEC(id, scene, ...) \
-  if (eq(d, ModelSpec<id>::dims()) && same_tree(SpecTree<id>::par, SpecTree<id>::npar)) return id;
+  if (eq(d, ModelSpec<id>::dims()) && SpecCyl<id>::n == ncylinder &&       \
+      same_tree(SpecTree<id>::par, SpecTree<id>::npar))                     \
+    return id;
 #include "specs.inc"
 #undef MJX_SPEC
   for (int i = 0; i < (int)rt_specs().size(); i++) {
     const RtSpec& r = rt_specs()[i];
-    if (eq(d, r.d) && same_tree(r.par.data(), (int)r.par.size())) return kRtSpecBase + i;
+    if (eq(d, r.d) && r.ncyl == ncylinder && same_tree(r.par.data(), (int)r.par.size())) return kRtSpecBase + i;
   }
   return 0;
 }

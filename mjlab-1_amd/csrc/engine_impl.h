@@ -1256,6 +1256,438 @@ __device__ __noinline__ int box_box(const ConOut& co, int key, int g1, int g2, c
   return nc;
 }
 
+// --------------------------------------------------------------------------- cylinder
+// Cylinder narrowphase (geom type 5: radius size[0], half length size[1], axis = column 2 of
+// its frame, as the capsule).  Plane, sphere and capsule partners are closed form (the capsule
+// up to a one-dimensional search); cylinder and box partners go through convex_pair below.
+// Signed distance of a cylinder-frame point to the cylinder (negative inside).
+__device__ __forceinline__ float cyl_sd(V3 q, float r, float h) {
+  const float dr = sqrtf(q.x * q.x + q.y * q.y) - r, dz = fabsf(q.z) - h;
+  const float pr = fmaxf(dr, 0.f), pz = fmaxf(dz, 0.f);
+  return sqrtf(pr * pr + pz * pz) + fminf(fmaxf(dr, dz), 0.f);
+}
+// Plane (geom g1: point pp, normal n) against the cylinder (centre c, frame R), MuJoCo's
+// mjc_PlaneCylinder restated: the axis a turned against the normal, v the radius vector of the
+// lowest rim direction; the near rim point, the far rim point, and two points of the near disk
+// 120 degrees either side (a triangle under an upright cylinder) -- each kept within the margin.
+__device__ __forceinline__ int plane_cylinder(const ConOut& co, int key, int g1, int g2, V3 pp, V3 n,
+                                              V3 c, const float* R, float r, float h, float margin) {
+  V3 a = {R[2], R[5], R[8]};
+  float na = dot(n, a);
+  if (na > 0.f) { a = a * -1.f; na = -na; }
+  V3 v = a * na - n;
+  const float len = norm(v);
+  // (a and n are unit to fp32 rounding: below 1e-6 the difference is that rounding, not a rim
+  // direction -- MuJoCo's 1e-15 holds only for an exactly upright frame in fp32)
+  v = len < 1e-6f ? V3{R[0], R[3], R[6]} * r : v * (r / len);
+  const float nv = dot(n, v), d0 = dot(n, c - pp);
+  const float d1 = d0 + h * na + nv;
+  if (d1 > margin) return 0;
+  append(co, key, g1, g2, d1, c + v + a * h - n * (0.5f * d1), n);
+  int k = 1;
+  const float d2 = d0 - h * na + nv;
+  if (d2 <= margin) append(co, key + k++, g1, g2, d2, c + v - a * h - n * (0.5f * d2), n);
+  const float d3 = d0 + h * na - 0.5f * nv;
+  if (d3 <= margin) {
+    V3 w = cross(v, a);
+    w = w * (r * 0.8660254038f / fmaxf(norm(w), MINVAL));
+    const V3 b = c + a * h - v * 0.5f - n * (0.5f * d3);
+    append(co, key + k++, g1, g2, d3, b + w, n);
+    append(co, key + k++, g1, g2, d3, b - w, n);
+  }
+  return k;
+}
+// Sphere (geom g1, centre `loc` in the cylinder's frame F) against the cylinder (geom g2):
+// outside, the cylinder point nearest the centre (side, cap or rim).  A centre inside is pushed
+// out through the nearer of cap and side, the cap where they tie within kBoxFaceTie (a segment
+// search inside ends on such ties, as in box_sphere); a centre on the axis has no radial
+// direction and takes the frame's x axis.  Normal from the sphere to the cylinder.
+__device__ __forceinline__ int sphere_cylinder(const ConOut& co, int key, int g1, int g2, const HFrame& F,
+                                               float r, float h, V3 loc, float rs, float margin) {
+  const float rho = sqrtf(loc.x * loc.x + loc.y * loc.y);
+  const float k = rho > r ? r / rho : 1.f;
+  const V3 cl = {loc.x * k, loc.y * k, fminf(fmaxf(loc.z, -h), h)};
+  const V3 dv = cl - loc;
+  const float dist = norm(dv);
+  if (dist - rs > margin) return 0;
+  V3 n, pos;
+  float cd;
+  if (dist > MINVAL) {
+    n = dv * (1.0f / dist);
+    pos = (cl + loc + n * rs) * 0.5f;
+    cd = dist - rs;
+  } else {
+    const float fc = h - fabsf(loc.z), fs = r - rho;
+    const bool cap = fc <= fs + kBoxFaceTie;
+    const float f = cap ? fc : fs;
+    if (cap) n = V3{0.f, 0.f, loc.z >= 0.f ? -1.f : 1.f};
+    else n = rho > MINVAL ? V3{-loc.x / rho, -loc.y / rho, 0.f} : V3{-1.f, 0.f, 0.f};
+    pos = loc + n * (0.5f * (rs - f));
+    cd = -f - rs;
+  }
+  append(co, key, g1, g2, cd, F.p + mulv(F.R, pos), mulv(F.R, n));
+  return 1;
+}
+// Capsule (geom g1: centre cw, unit axis aw, half length hl, radius rc; world frame) against
+// the cylinder: sphere-cylinder contacts at points of the capsule's segment.  The signed
+// distance along the segment is convex.  A segment along the side (outside it) or across a cap
+// (above it) within capsule_capsule's parallel band has a whole stretch of minimisers: the two
+// ends of that stretch are the contacts.  Otherwise box_capsule's search: the golden-section
+// minimiser where it is deeper than both ends by kCylMidEps, with the deeper end; else the ends.
+// (The flat stretches are taken out above, so the band is the search's own resolution, not
+// box_capsule's kBoxMidEps: the deepest contact reports the pair's distance to 1e-6.)
+constexpr float kCylMidEps = 1e-6f;
+__device__ __forceinline__ int capsule_cylinder(const ConOut& co, int key, int g1, int g2, const HFrame& F,
+                                                float r, float h, V3 cw, V3 aw, float hl, float rc,
+                                                float margin) {
+  const V3 c = mulTv(F.R, cw - F.p), a = mulTv(F.R, aw);
+  if (cyl_sd(c, r, h) - hl - rc > margin) return 0;
+  const float axy2 = a.x * a.x + a.y * a.y, cxy2 = c.x * c.x + c.y * c.y;
+  float lo = 1.f, hi = -1.f;
+  if (axy2 * hl * hl * h * h < MINVAL) {
+    if (cxy2 > r * r) {
+      const float tc = a.z >= 0.f ? -c.z : c.z;
+      lo = fmaxf(-hl, tc - h); hi = fminf(hl, tc + h);
+    }
+  } else if (a.z * a.z * hl * hl * r * r < MINVAL && fabsf(c.z) > h) {
+    const float b = c.x * a.x + c.y * a.y, disc = b * b - axy2 * (cxy2 - r * r);
+    if (disc > 0.f) {
+      const float sq = sqrtf(disc);
+      lo = fmaxf(-hl, (-b - sq) / axy2); hi = fminf(hl, (-b + sq) / axy2);
+    }
+  }
+  int n = 0;
+  if (lo < hi) {
+    n += sphere_cylinder(co, key, g1, g2, F, r, h, c + a * lo, rc, margin);
+    n += sphere_cylinder(co, key + n, g1, g2, F, r, h, c + a * hi, rc, margin);
+    return n;
+  }
+  const V3 e0 = c - a * hl, e1 = c + a * hl;
+  const float sd0 = cyl_sd(e0, r, h), sd1 = cyl_sd(e1, r, h);
+  const float ig = 0.6180339887f;
+  lo = -hl; hi = hl;
+  float x1 = hi - ig * (hi - lo), x2 = lo + ig * (hi - lo);
+  float f1 = cyl_sd(c + a * x1, r, h), f2 = cyl_sd(c + a * x2, r, h);
+  for (int it = 0; it < kBoxGolden; it++) {
+    if (f1 <= f2) {
+      hi = x2; x2 = x1; f2 = f1;
+      x1 = hi - ig * (hi - lo);
+      f1 = cyl_sd(c + a * x1, r, h);
+    } else {
+      lo = x1; x1 = x2; f1 = f2;
+      x2 = lo + ig * (hi - lo);
+      f2 = cyl_sd(c + a * x2, r, h);
+    }
+  }
+  const V3 em = c + a * (0.5f * (lo + hi));
+  if (cyl_sd(em, r, h) < fminf(sd0, sd1) - kCylMidEps) {
+    n += sphere_cylinder(co, key, g1, g2, F, r, h, em, rc, margin);
+    n += sphere_cylinder(co, key + n, g1, g2, F, r, h, sd0 <= sd1 ? e0 : e1, rc, margin);
+  } else {
+    n += sphere_cylinder(co, key, g1, g2, F, r, h, e0, rc, margin);
+    n += sphere_cylinder(co, key + n, g1, g2, F, r, h, e1, rc, margin);
+  }
+  return n;
+}
+
+// The two convex solids, shape frame: the support mapping (a farthest point along d) and the
+// projection (the point of the solid nearest p), both closed form.
+struct CylSupport {
+  float r, h;
+  __device__ __forceinline__ V3 operator()(V3 d) const {
+    const float rho = sqrtf(d.x * d.x + d.y * d.y);
+    const float s = rho > 1e-20f ? r / rho : 0.f;
+    return {d.x * s, d.y * s, d.z >= 0.f ? h : -h};
+  }
+  __device__ __forceinline__ V3 proj(V3 p) const {
+    const float rho = sqrtf(p.x * p.x + p.y * p.y);
+    const float k = rho > r ? r / rho : 1.f;
+    return {p.x * k, p.y * k, fminf(fmaxf(p.z, -h), h)};
+  }
+};
+struct BoxSupport {
+  V3 s;
+  __device__ __forceinline__ V3 operator()(V3 d) const {
+    return {d.x >= 0.f ? s.x : -s.x, d.y >= 0.f ? s.y : -s.y, d.z >= 0.f ? s.z : -s.z};
+  }
+  __device__ __forceinline__ V3 proj(V3 p) const {
+    return {fminf(fmaxf(p.x, -s.x), s.x), fminf(fmaxf(p.y, -s.y), s.y), fminf(fmaxf(p.z, -s.z), s.z)};
+  }
+};
+// Closest point of the triangle a b c to the origin, as barycentric weights (Voronoi regions).
+__device__ __forceinline__ void tri_origin(V3 a, V3 b, V3 c, float& u, float& v, float& w) {
+  const V3 ab = b - a, ac = c - a;
+  const float d1 = -dot(ab, a), d2 = -dot(ac, a);
+  const float d3 = -dot(ab, b), d4 = -dot(ac, b);
+  const float d5 = -dot(ab, c), d6 = -dot(ac, c);
+  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  u = v = w = 0.f;
+  // a sliver (support points along one rim or edge): the nearest of its three edges, the
+  // interior weights would divide by its vanishing area
+  const V3 nt = cross(ab, ac);
+  if (dot(nt, nt) <= 1e-8f * dot(ab, ab) * dot(ac, ac)) {
+    const V3 bc = c - b;
+    const float tab = clamp01(d1 / fmaxf(dot(ab, ab), 1e-30f)), tac = clamp01(d2 / fmaxf(dot(ac, ac), 1e-30f));
+    const float tbc = clamp01(-dot(bc, b) / fmaxf(dot(bc, bc), 1e-30f));
+    const V3 pab = a + ab * tab, pac = a + ac * tac, pbc = b + bc * tbc;
+    const float qab = dot(pab, pab), qac = dot(pac, pac), qbc = dot(pbc, pbc);
+    if (qab <= qac && qab <= qbc) { u = 1.f - tab; v = tab; }
+    else if (qac <= qbc) { u = 1.f - tac; w = tac; }
+    else { v = 1.f - tbc; w = tbc; }
+    return;
+  }
+  if (d1 <= 0.f && d2 <= 0.f) { u = 1.f; return; }
+  if (d3 >= 0.f && d4 <= d3) { v = 1.f; return; }
+  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { v = d1 / (d1 - d3); u = 1.f - v; return; }
+  if (d6 >= 0.f && d5 <= d6) { w = 1.f; return; }
+  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { w = d2 / (d2 - d6); u = 1.f - w; return; }
+  if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {
+    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.f - w; return;
+  }
+  const float den = 1.0f / (va + vb + vc);
+  v = vb * den; w = vc * den; u = 1.f - v - w;
+}
+// Two convex solids through their support mappings: geom g1 (frame F1, support S1) against geom
+// g2 (F2, S2), one contact.  All of it in F1's frame on the difference body M = A - B
+// (support s_A(d) - s_B(-d)), one lane, registers only: at most four support points and the
+// points of A they came from.
+//   GJK (separated): the point v of the simplex nearest the origin, a support point along -v
+// added, the simplex cut to the face that holds v (Voronoi regions).  v . w / |v| bounds the
+// distance from below: past the margin there is no contact.  Stopped at |v|^2 - v . w <=
+// kGjkRel |v| |w| (what fp32 resolves of that gap), at no progress, or after kGjkIter supports.
+// The origin inside a tetrahedron, or |v| < 1e-6: overlapping.  The distance is then good to
+// second order but the direction only to first (1e-2 at a 4 mm gap), and fp32 GJK gets no
+// further, so the witness points are polished: kPolish rounds of the two exact projections (onto
+// B, then onto A -- a contraction towards the closest pair, exact in one round for a vertex
+// or rim point over a face); dist and n are the polished points' difference.
+//   Portal refinement (overlapping; Snethen's MPR): a ray from an interior point of M through the
+// origin, a triangle of support points it passes through pushed outward to M's surface (each
+// loop bounded: kMprFind, kMprIter).  The portal's normal n and the support depth h_M(n) are
+// the contact's normal and -dist.  The first ray comes from the centres; kMprPass - 1 further
+// passes shoot it along the last normal (from -n h_M(n) / 64, interior while the depth along n
+// is within 64 x the least), which ends on a direction whose supporting face holds the origin's
+// foot -- a local minimum of the depth, where both witness points lie on their shapes; it is
+// not the global minimiser in general.  The witness on A starts from the ray's hit point in the
+// portal (weights applied to A's points) and is polished like the separated pair's.
+constexpr float kGjkRel = 4e-7f;
+constexpr int kGjkIter = 40;
+constexpr int kPolish = 96;
+constexpr int kMprFind = 12;
+constexpr int kMprIter = 28;
+constexpr int kMprPass = 8;
+constexpr float kMprTol = 2e-7f;
+template <class S1, class S2>
+__device__ __noinline__ int convex_pair(const ConOut& co, int key, int g1, int g2, const HFrame& F1,
+                                        S1 s1, const HFrame& F2, S2 s2, float margin) {
+  const V3 c = mulTv(F1.R, F2.p - F1.p);
+  V3 b[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) b[j] = mulTv(F1.R, V3{F2.R[j], F2.R[3 + j], F2.R[6 + j]});
+  // support of M along the unit direction d: the point w of M and the point a of A
+  auto sup = [&](V3 d, V3& w, V3& a) {
+    a = s1(d);
+    const V3 q = s2(V3{-dot(d, b[0]), -dot(d, b[1]), -dot(d, b[2])});
+    w = a - (c + b[0] * q.x + b[1] * q.y + b[2] * q.z);
+  };
+  auto unit = [](V3 d) { return d * (1.0f / fmaxf(norm(d), 1e-30f)); };
+  V3 W[4], A[4];
+  float lam[4] = {0.f, 0.f, 0.f, 0.f};
+  int ns = 0;
+  V3 v = c * -1.f;
+  if (dot(v, v) < 1e-12f) v = V3{1e-3f, 0.f, 0.f};
+  bool pen = false;
+  for (int it = 0; it < kGjkIter; it++) {
+    const float vv = dot(v, v);
+    V3 w, a;
+    sup(v * (-1.0f / sqrtf(vv)), w, a);
+    const float vw = dot(v, w);
+    if (vw > 0.f && vw > margin * sqrtf(vv)) return 0;
+    if (ns > 0 && vv - vw <= kGjkRel * sqrtf(vv) * fmaxf(norm(w), 1e-3f)) break;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (j == ns) { W[j] = w; A[j] = a; }
+    ns++;
+    // the point of the simplex nearest the origin, as weights
+#pragma unroll
+    for (int j = 0; j < 4; j++) lam[j] = 0.f;
+    if (ns == 1) {
+      lam[0] = 1.f;
+    } else if (ns == 2) {
+      const V3 e = W[1] - W[0];
+      const float t = clamp01(-dot(W[0], e) / fmaxf(dot(e, e), 1e-30f));
+      lam[0] = 1.f - t; lam[1] = t;
+    } else if (ns == 3) {
+      tri_origin(W[0], W[1], W[2], lam[0], lam[1], lam[2]);
+    } else {
+      // each face the origin lies outside of (seen from the fourth vertex); none: inside
+      float best = 1e30f;
+      bool outside = false;
+#pragma unroll
+      for (int f = 0; f < 4; f++) {
+        const int i0 = (f + 1) & 3, i1 = (f + 2) & 3, i2 = (f + 3) & 3;
+        const V3 nf = cross(W[i1] - W[i0], W[i2] - W[i0]);
+        const V3 ef = W[f] - W[i0];
+        const float ds = dot(nf, ef), dor = -dot(nf, W[i0]);
+        // (a flat tetrahedron -- four support points of one face -- has no inside: every face
+        // of it stays a candidate)
+        const bool flat = ds * ds <= 1e-8f * dot(nf, nf) * dot(ef, ef);
+        if (!flat && ds * dor >= 0.f) continue;
+        outside = true;
+        float u0, u1, u2;
+        tri_origin(W[i0], W[i1], W[i2], u0, u1, u2);
+        const V3 p = W[i0] * u0 + W[i1] * u1 + W[i2] * u2;
+        const float pp = dot(p, p);
+        if (pp < best) {
+          best = pp;
+#pragma unroll
+          for (int j = 0; j < 4; j++) lam[j] = j == i0 ? u0 : (j == i1 ? u1 : (j == i2 ? u2 : 0.f));
+        }
+      }
+      if (!outside) { pen = true; break; }
+    }
+    // keep the vertices that carry weight
+    V3 nW[4], nA[4];
+    float nl[4] = {0.f, 0.f, 0.f, 0.f};
+    int m = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      if (i < ns && lam[i] > 0.f) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (j == m) { nW[j] = W[i]; nA[j] = A[i]; nl[j] = lam[i]; }
+        m++;
+      }
+    }
+    V3 nv = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (j < m) { W[j] = nW[j]; A[j] = nA[j]; nv = nv + nW[j] * nl[j]; }
+      lam[j] = nl[j];
+    }
+    ns = m;
+    const float nvv = dot(nv, nv);
+    if (nvv < 1e-12f) { pen = true; break; }
+    if (nvv >= vv && it > 0) break;  // rounding: no closer than before
+    v = nv;
+  }
+  V3 n, pa;
+  float depth = 0.f;
+  if (!pen) {
+    pa = V3{0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (j < ns) pa = pa + A[j] * lam[j];
+    n = v * (-1.0f / fmaxf(norm(v), 1e-30f));
+  } else {
+    V3 v0 = c * -1.f;
+    if (dot(v0, v0) < 1e-12f) v0 = V3{1e-5f, 0.f, 0.f};
+    n = unit(v0 * -1.f);
+    pa = V3{0.f, 0.f, 0.f};
+    for (int pass = 0; pass < kMprPass; pass++) {
+      const V3 ray = unit(v0 * -1.f);
+      V3 v1, a1, v2, a2, v3p, a3, v4, a4;
+      sup(ray, v1, a1);
+      V3 dir = cross(v1, v0);
+      if (dot(dir, dir) < 1e-24f * dot(v1, v1)) {  // the ray leaves M through v1 itself
+        n = ray; depth = dot(v1, ray); pa = a1;
+        break;
+      }
+      sup(unit(dir), v2, a2);
+      dir = cross(v1 - v0, v2 - v0);
+      if (dot(dir, v0) > 0.f) {
+        const V3 tv = v1, ta = a1;
+        v1 = v2; a1 = a2; v2 = tv; a2 = ta;
+        dir = dir * -1.f;
+      }
+      sup(unit(dir), v3p, a3);
+      for (int it = 0; it < kMprFind; it++) {
+        if (dot(cross(v1, v3p), v0) < 0.f) { v2 = v3p; a2 = a3; dir = cross(v1 - v0, v3p - v0); }
+        else if (dot(cross(v3p, v2), v0) < 0.f) { v1 = v3p; a1 = a3; dir = cross(v3p - v0, v2 - v0); }
+        else break;
+        sup(unit(dir), v3p, a3);
+      }
+      for (int it = 0; it < kMprIter; it++) {
+        dir = unit(cross(v2 - v1, v3p - v1));
+        sup(dir, v4, a4);
+        if (dot(v4 - v3p, dir) <= kMprTol) break;
+        const V3 cr = cross(v4, v0);
+        if (dot(v1, cr) > 0.f) {
+          if (dot(v2, cr) > 0.f) { v1 = v4; a1 = a4; } else { v3p = v4; a3 = a4; }
+        } else {
+          if (dot(v3p, cr) > 0.f) { v2 = v4; a2 = a4; } else { v1 = v4; a1 = a4; }
+        }
+      }
+      n = dir;
+      depth = dot(v4, dir);
+      // the ray's hit point x in the portal's plane, its weights in the triangle (clamped)
+      const float den = dot(dir, ray);
+      const V3 x = ray * (dot(dir, v1) / (fabsf(den) > 1e-12f ? den : 1e-12f));
+      float u0, u1, u2;
+      tri_origin(v1 - x, v2 - x, v3p - x, u0, u1, u2);
+      pa = a1 * u0 + a2 * u1 + a3 * u2;
+      v0 = dir * (-depth * (1.0f / 64.0f));
+      if (depth <= 1e-9f) break;
+    }
+  }
+  // the witness points: kPolish rounds of the two exact projections between A and B -- B moved
+  // out by the depth along n when they overlap, so that the two touch and the points meet on
+  // the contact set (an error of n then moves them to second order only)
+  // The rounds contract linearly (slowly between nearly parallel faces): every 32nd round the
+  // point on A jumps to the limit of the geometric sequence its last two steps suggest
+  // (Aitken), and the next round puts it back onto the shapes.
+  const V3 cs = c + n * depth;
+  V3 pb = pa, p1 = pa, p2 = pa;
+  for (int it = 0; it < kPolish; it++) {
+    const V3 l = pa - cs;
+    const V3 q = s2.proj(V3{dot(l, b[0]), dot(l, b[1]), dot(l, b[2])});
+    pb = cs + b[0] * q.x + b[1] * q.y + b[2] * q.z;
+    p2 = p1; p1 = pa;
+    pa = s1.proj(pb);
+    const V3 st = pa - p1;
+    if (dot(st, st) < 1e-18f) break;  // the rounds have stopped moving
+    if ((it & 31) == 31 && it + 1 < kPolish) {
+      const V3 e1 = pa - p1, e2 = p1 - p2;
+      const float q1 = dot(e1, e1), q2 = dot(e2, e2);
+      if (q2 > 1e-20f && q1 < 0.998f * q2) {
+        const float rho = sqrtf(q1 / q2);
+        pa = pa + e1 * (rho / (1.f - rho));
+      }
+    }
+  }
+  float dist = -depth;
+  if (!pen) {
+    const V3 dv = pb - pa;
+    dist = norm(dv);
+    if (dist > margin) return 0;
+    if (dist > 1e-9f) n = dv * (1.0f / dist);
+  }
+  // midway between the point on A and the point on B (moved back by the depth)
+  append(co, key, g1, g2, dist, F1.p + mulv(F1.R, (pa + pb) * 0.5f - n * (0.5f * depth)), mulv(F1.R, n));
+  return 1;
+}
+
+// Every pair with a cylinder (types t1 <= t2, frames F1 / F2, sizes s1 / s2), out of line so
+// that the collision loops carry one call instead of four routines' registers.  -1: a pair
+// kind without a routine (the caller raises the unsupported-pair flag).
+__device__ __noinline__ int cylinder_pair(const ConOut& co, int key, int g1, int g2, int t1, int t2,
+                                          const HFrame& F1, const float* s1, const HFrame& F2,
+                                          const float* s2, float margin) {
+  if (t2 == GEOM_CYLINDER) {
+    if (t1 == GEOM_PLANE)
+      return plane_cylinder(co, key, g1, g2, F1.p, V3{F1.R[2], F1.R[5], F1.R[8]}, F2.p, F2.R, s2[0], s2[1], margin);
+    if (t1 == GEOM_SPHERE)
+      return sphere_cylinder(co, key, g1, g2, F2, s2[0], s2[1], mulTv(F2.R, F1.p - F2.p), s1[0], margin);
+    if (t1 == GEOM_CAPSULE)
+      return capsule_cylinder(co, key, g1, g2, F2, s2[0], s2[1], F1.p, V3{F1.R[2], F1.R[5], F1.R[8]}, s1[1],
+                              s1[0], margin);
+    if (t1 == GEOM_CYLINDER)
+      return convex_pair(co, key, g1, g2, F1, CylSupport{s1[0], s1[1]}, F2, CylSupport{s2[0], s2[1]}, margin);
+  } else if (t1 == GEOM_CYLINDER && t2 == GEOM_BOX) {
+    return convex_pair(co, key, g1, g2, F1, CylSupport{s1[0], s1[1]}, F2, BoxSupport{v3(s2)}, margin);
+  }
+  return -1;
+}
+
 // --------------------------------------------------------------------------- impedance
 __device__ __forceinline__ float impedance(const float* si, float pos, float margin) {
   float dmin = fminf(MAXIMP, fmaxf(MINIMP, si[0])), dmax = fminf(MAXIMP, fmaxf(MINIMP, si[1]));
@@ -1390,6 +1822,17 @@ template <int SP> struct ModelSpec {
 template <int SP> constexpr int spec_nr() { return nr_for_nv(ModelSpec<SP>::dims().nv); }
 // box-box narrowphase compiled in: generic kernels, and specialisations with such pairs
 template <int SP> constexpr bool kBoxBox = SP == 0 || ModelSpec<SP>::dims().nboxbox > 0;
+// cylinder narrowphase compiled in: the generic kernels, and a run-time specialisation of a model
+// with cylinder pairs.  The pair count is not in Dims (its 22-int layout is the JIT libraries'
+// ABI): a generated specs file carries it as MJX_SPEC_CYL(id, pairs), the library exports it
+// (jit.hip mjx_jit_ncyl) and find_spec matches it.  No shipped entry has one, so the shipped
+// specialisations, and a JIT kernel of a cylinder-free model, compile without the code.
+template <int SP> struct SpecCyl { static constexpr int n = 0; };
+#define MJX_SPEC_CYL(id, k)                                                   \
+  template <> struct SpecCyl<id> { static constexpr int n = k; };
+#include MJX_SPECS_FILE
+#undef MJX_SPEC_CYL
+template <int SP> constexpr bool kCylinder = SP == 0 || SpecCyl<SP>::n > 0;
 // at most one contact per lane of the world's wave (every fast carve, nconmax <= 64): the
 // contact loops of phases A and C are then the single lane-per-contact pass; a max carve past
 // 64 contacts (sim.max_capacity: the reference's njmax bounds a world's contacts too) takes
@@ -3244,7 +3687,13 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const float* s1 = gsize + 3 * g1;
         const float* s2 = gsize + 3 * g2;
         int key = p * 8;
-        if (t1 == GEOM_PLANE) {
+        if (kCylinder<SP> && (t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER)) {
+          // every cylinder pair behind one call: the loop keeps its registers (as box_box)
+          HFrame F1, F2;
+          F1.p = p1; F2.p = p2;
+          for (int i = 0; i < 9; i++) { F1.R[i] = S[L.gxmat + 9 * l1 + i]; F2.R[i] = S[L.gxmat + 9 * l2 + i]; }
+          if (cylinder_pair(co, key, g1, g2, t1, t2, F1, s1, F2, s2, margin) < 0) atomicOr(&ints[3], 4);
+        } else if (t1 == GEOM_PLANE) {
           const float* Rp = S + L.gxmat + 9 * l1;
           V3 n = {Rp[2], Rp[5], Rp[8]};
           if (t2 == GEOM_SPHERE) {
@@ -3397,6 +3846,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
                       if (pa == sg) box_box(co, key, pa, pb, F, bs, Fp, v3(s1), margin);
                       else box_box(co, key, pa, pb, Fp, v3(s1), F, bs, margin);
                     }
+                  } else if (kCylinder<SP> && t1 == GEOM_CYLINDER) {
+                    HFrame Fp;
+                    Fp.p = p1;
+                    for (int i = 0; i < 9; i++) Fp.R[i] = S[L.gxmat + 9 * l1 + i];
+                    cylinder_pair(co, key, g1, sg, GEOM_CYLINDER, GEOM_BOX, Fp, s1, F, gsize + 3 * sg, margin);
                   } else {
                     atomicOr(&ints[3], 4);
                   }

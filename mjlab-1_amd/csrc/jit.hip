@@ -26,6 +26,10 @@ extern "C" __attribute__((visibility("default"))) unsigned long long mjx_jit_hdr
 extern "C" __attribute__((visibility("default"))) void mjx_jit_dims(mjx::Dims* out) {
   *out = mjx::ModelSpec<MJX_JIT_ID>::dims();
 }
+// candidate pairs with a cylinder geom the kernels were compiled for (0: no cylinder narrowphase)
+extern "C" __attribute__((visibility("default"))) int mjx_jit_ncyl(void) {
+  return mjx::SpecCyl<MJX_JIT_ID>::n;
+}
 extern "C" __attribute__((visibility("default"))) int mjx_jit_tree(int* par, int cap) {
   const int n = mjx::SpecTree<MJX_JIT_ID>::npar;
   for (int i = 0; i < n && i < cap; i++) par[i] = mjx::SpecTree<MJX_JIT_ID>::par[i];

@@ -24,6 +24,8 @@ struct ModelTables {
   int nmaskword = 0;
   int neq = 0;     // joint equalities (fields.h counts the eq_* fields by it)
   int max_condim = 3;  // largest geom_condim, at least 3 (check_condims; engine.h DModel::max_condim)
+  int ncylinder = 0;  // candidate pairs with a cylinder: such a model runs the generic kernels
+                      // (engine_impl.h kCylinder; not in Dims, whose layout the JIT ABI fixes)
   int ncsens = 0;  // 0 past 64 single-slot contact sensors (phase C then matches serially)
   std::vector<int32_t> dof_parentid;  // as given: find_spec checks a specialisation's dof tree
   // engine.h DModel, the host-derived part
@@ -308,8 +310,12 @@ inline std::string terrain_blocks(const mjxModelDesc& desc, ModelTables& t) {
   d.npair = nreg;
   d.npair_all = np;
   d.nboxbox = 0;
-  for (int q = 0; q < np; q++)
-    d.nboxbox += desc.geom_type[desc.pair_geom1[q]] == GEOM_BOX && desc.geom_type[desc.pair_geom2[q]] == GEOM_BOX;
+  t.ncylinder = 0;
+  for (int q = 0; q < np; q++) {
+    const int t1 = desc.geom_type[desc.pair_geom1[q]], t2 = desc.geom_type[desc.pair_geom2[q]];
+    d.nboxbox += t1 == GEOM_BOX && t2 == GEOM_BOX;
+    t.ncylinder += t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER;
+  }
   d.nstatic = (int)t.st_geom.size();
   d.nstpartner = (int)t.st_partner.size();
   return "";

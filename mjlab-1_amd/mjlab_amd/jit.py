@@ -75,6 +75,16 @@ def spec_dims(m) -> dict:
               nconmax=0, njmax=0)
 
 
+def cylinder_pairs(m) -> int:
+  """Candidate pairs of the compiled model with a cylinder geom (type 5): what
+  csrc/model_tables.h counts as ModelTables::ncylinder.  Kernels specialised for such a model
+  are compiled with the cylinder narrowphase (the MJX_SPEC_CYL line of its specs file)."""
+  a = m.arrays
+  gt = np.asarray(a.get("geom_type", ())).reshape(-1)
+  p1, p2 = (np.asarray(a.get(k, ()), dtype=np.int64).reshape(-1) for k in ("pair_geom1", "pair_geom2"))
+  return int(((gt[p1] == 5) | (gt[p2] == 5)).sum()) if len(p1) else 0
+
+
 def dof_tree(m) -> tuple:
   return tuple(int(p) for p in np.asarray(m.dof_parentid).reshape(-1))
 
@@ -87,20 +97,26 @@ GUARD_HEAD = ["#ifndef MJX_SPEC", "#define MJX_SPEC(...)", "#define MJX_SPEC_DEF
               "// MJX_SPEC_ROLE(id, mask): 1 = a fast carve, 2 = a max (re-solve) carve; the kernels",
               "// only one role launches are left out of that entry (the generic ones stand in)",
               "#ifndef MJX_SPEC_ROLE", "#define MJX_SPEC_ROLE(...)", "#define MJX_SPEC_ROLE_DEFAULTED",
-              "#endif"]
+              "#endif",
+              "// MJX_SPEC_CYL(id, pairs): candidate pairs with a cylinder geom (kernels with its narrowphase)",
+              "#ifndef MJX_SPEC_CYL", "#define MJX_SPEC_CYL(...)", "#define MJX_SPEC_CYL_DEFAULTED", "#endif"]
 GUARD_TAIL = ["#ifdef MJX_SPEC_DEFAULTED", "#undef MJX_SPEC", "#undef MJX_SPEC_DEFAULTED", "#endif",
               "#ifdef MJX_SPEC_TREE_DEFAULTED", "#undef MJX_SPEC_TREE", "#undef MJX_SPEC_TREE_DEFAULTED",
               "#endif",
               "#ifdef MJX_SPEC_ROLE_DEFAULTED", "#undef MJX_SPEC_ROLE", "#undef MJX_SPEC_ROLE_DEFAULTED",
-              "#endif"]
+              "#endif",
+              "#ifdef MJX_SPEC_CYL_DEFAULTED", "#undef MJX_SPEC_CYL", "#undef MJX_SPEC_CYL_DEFAULTED", "#endif"]
 
 
-def entry_lines(sid: int, name: str, dims: dict, par: tuple, role: int | None = None) -> list[str]:
+def entry_lines(sid: int, name: str, dims: dict, par: tuple, role: int | None = None,
+                ncyl: int = 0) -> list[str]:
   """One specs.inc entry (scripts/gen_specs.py writes the shipped table from the same)."""
   out = [f"MJX_SPEC({sid}, {name}, " + ", ".join(str(int(dims[k])) for k in ORDER) + ")",
          f"MJX_SPEC_TREE({sid}, " + ", ".join(str(p) for p in par) + ")"]
   if role is not None:
     out.append(f"MJX_SPEC_ROLE({sid}, {role})")
+  if ncyl > 0:
+    out.append(f"MJX_SPEC_CYL({sid}, {ncyl})")
   return out
 
 
@@ -133,11 +149,12 @@ def library_path(model, nconmax: int, njmax: int, role: int) -> tuple[str, str, 
   d = spec_dims(model)
   d["nconmax"], d["njmax"] = int(nconmax), int(njmax)
   par = dof_tree(model)
-  body = "\n".join(entry_lines(0, "jit", d, par, role))
+  ncyl = cylinder_pairs(model)
+  body = "\n".join(entry_lines(0, "jit", d, par, role, ncyl))
   key = hashlib.sha1((body + _source_hash()).encode()).hexdigest()[:20]
   # an entry id of its own (template instantiations named apart from every other library's)
   sid = 2000 + int(key[:6], 16) % 900000
-  text = "\n".join(GUARD_HEAD + entry_lines(sid, "jit", d, par, role) + GUARD_TAIL) + "\n"
+  text = "\n".join(GUARD_HEAD + entry_lines(sid, "jit", d, par, role, ncyl) + GUARD_TAIL) + "\n"
   return os.path.join(CACHE, f"spec_{key}.so"), text, sid
 
 
