@@ -92,9 +92,9 @@ struct Capacity {
 };
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
-static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_parentid, int neq,
-                         int max_condim, int cone, int ncylinder, const char* too_big, Capacity& c) {
-  c.d = d;
+static int make_capacity(const mjx::SpecKey& key, int neq, int max_condim, int cone,
+                         const char* too_big, Capacity& c) {
+  const mjx::Dims& d = c.d = key.d;
   for (int i = 0; i < 3; i++) {
     // (phases A and C hold the contacts' friction coefficients: five each with torsional or
     // rolling contacts in the model)
@@ -102,11 +102,7 @@ static int make_capacity(const mjx::Dims& d, const std::vector<int32_t>& dof_par
     c.lds[i] = mjx::make_lds(d, i, false, mjx::con_mu_width(max_condim), cone);
     if ((size_t)c.lds[i].total * 4 > 160 * 1024) return fail(too_big);
   }
-  // a model with joint equalities runs the generic kernels: no specialisation holds the
-  // equality rows' code (engine_impl.h neq_of), and none the rotational contact rows' (condim_of)
-  // ... and none the elliptic cone's rows and solver (cone_of).  The cylinder narrowphase is in
-  // the run-time specialisations compiled for a model with cylinder pairs only (kCylinder)
-  c.spec = neq > 0 || max_condim > 3 || cone != 0 ? 0 : mjx::find_spec(d, dof_parentid.data(), ncylinder);
+  c.spec = mjx::spec_can_hold(neq, max_condim, cone) ? mjx::find_spec(key) : 0;
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -369,11 +365,8 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   s->model = model;
   s->nworld = nworld;
   s->dm = model->dm;
-  mjx::Dims dims = model->t.d;
-  dims.nconmax = nconmax;
-  dims.njmax = njmax;
-  if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                    model->t.o.cone, model->t.ncylinder, "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
+  if (make_capacity(model->t.spec_key(nconmax, njmax), model->t.neq, model->t.max_condim, model->t.o.cone,
+                    "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
   // An elliptic model runs without Newton row classes: a class launch copies the pack's row
   // slots region by region into its smaller carve, and the grouping words (carve.h make_lds)
@@ -395,10 +388,8 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
                (s->side.nsplit == 1 || s->nrowclass == 0);
   s->con_stride = s->has_big ? nconmax_max : nconmax;
   if (s->has_big) {
-    dims.nconmax = nconmax_max;
-    dims.njmax = njmax_max;
-    if (make_capacity(dims, model->t.dof_parentid, model->t.neq, model->t.max_condim,
-                      model->t.o.cone, model->t.ncylinder, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
+    if (make_capacity(model->t.spec_key(nconmax_max, njmax_max), model->t.neq, model->t.max_condim,
+                      model->t.o.cone, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed
     s->ovf_cap = nworld;
@@ -884,35 +875,24 @@ int mjx_spec_register(const char* path) {
   if (!path) return fail("null path");
   void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
   if (!h) return fail(std::string("dlopen: ") + dlerror());
-  using AbiFn = int (*)(void);
-  using DimsFn = void (*)(mjx::Dims*);
-  using TreeFn = int (*)(int*, int);
+  using DescribeFn = void (*)(mjx::JitInfo*);
   using KernFn = mjx::StepFnPtr (*)(int);
-  auto abi = reinterpret_cast<AbiFn>(dlsym(h, "mjx_jit_abi"));
-  auto dims = reinterpret_cast<DimsFn>(dlsym(h, "mjx_jit_dims"));
-  auto tree = reinterpret_cast<TreeFn>(dlsym(h, "mjx_jit_tree"));
+  auto describe = reinterpret_cast<DescribeFn>(dlsym(h, "mjx_jit_describe"));
   auto kern = reinterpret_cast<KernFn>(dlsym(h, "mjx_jit_kernel"));
-  if (!abi || !dims || !tree || !kern) return fail(std::string(path) + ": not a jit.hip library");
-  if (abi() != (int)sizeof(mjx::Dims)) return fail(std::string(path) + ": Dims layout mismatch (stale build)");
+  if (!describe || !kern) return fail(std::string(path) + ": not a jit.hip library");
+  mjx::JitInfo info{};
+  info.size = (int)sizeof(info);
+  describe(&info);
+  if (info.size != (int)sizeof(info)) return fail(std::string(path) + ": Dims layout mismatch (stale build)");
   // the kernels read Params / Lds / DData through this library's layout: the JIT library must
   // come from the same kernel headers (csrc/Makefile MJX_HDR_HASH), else a stale cache entry or
   // a header edited after the last engine build would fault the device instead of failing here
-  using HdrFn = unsigned long long (*)(void);
-  auto hdr = reinterpret_cast<HdrFn>(dlsym(h, "mjx_jit_hdr"));
 #ifdef MJX_HDR_HASH
-  if (!hdr || hdr() != (unsigned long long)MJX_HDR_HASH)
+  if (info.hdr != (unsigned long long)MJX_HDR_HASH)
     return fail(std::string(path) + ": built from other kernel headers than libmjx355.so (rebuild one of them)");
-#else
-  if (!hdr) return fail(std::string(path) + ": not a jit.hip library of this engine");
 #endif
-  mjx::Dims d{};
-  dims(&d);
-  int par[64];
-  const int n = tree(par, 64);
-  if (n < 0 || n > 64) return fail("bad dof tree in the jit library");
-  // (optional entry point: a library without it holds no cylinder narrowphase)
-  auto ncyl = reinterpret_cast<AbiFn>(dlsym(h, "mjx_jit_ncyl"));
-  return mjx::register_spec(d, par, n, kern, ncyl ? ncyl() : 0);  // the library stays loaded for the process
+  if (info.key.npar < 0 || info.key.npar > mjx::kMaxDof) return fail("bad dof tree in the jit library");
+  return mjx::register_spec(info.key, kern);  // the library stays loaded for the process
 }
 
 int mjx_sim_mass_matrix(mjxSim* s, int big, float* out, void* stream) {

@@ -235,8 +235,8 @@ constexpr bool jg_carve_agrees(const Dims& d) {
 #else
 #define MJX_CARVE_SPECS_FILE "specs.inc"
 #endif
-#define MJX_SPEC(id, scene, ...)                           \
-  static_assert(jg_carve_agrees(Dims{__VA_ARGS__}),        \
+#define MJX_SPEC(id, scene, role, ncyl, dims, par)               \
+  static_assert(jg_carve_agrees(Dims{MJX_UNPAREN(dims)}),        \
                 "spec " #id ": the J-in-global carve moves a B-pack offset before efc_J");
 #include MJX_CARVE_SPECS_FILE
 #undef MJX_SPEC

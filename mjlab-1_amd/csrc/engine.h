@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "fields.h"
 
@@ -55,6 +56,9 @@ struct Dims {
   int nconmax;  // contacts per world held in LDS
   int njmax;    // constraint rows per world held in LDS
 };
+// MJX_UNPAREN((a, b, c)) is a, b, c: the parenthesised lists of a specs.inc MJX_SPEC line
+#define MJX_UNPAREN_(...) __VA_ARGS__
+#define MJX_UNPAREN(list) MJX_UNPAREN_ list
 
 struct Opt {
   float timestep, tolerance, ls_tolerance, impratio, meaninertia;
@@ -108,10 +112,8 @@ struct DModel {
   const int32_t* cs_sensor;
   const uint64_t* geom_csmask1;
   const uint64_t* geom_csmask2;
-  // Joint equalities (two constraint rows each): the eq_* fields of fields.h and their count.
-  // The count is not in Dims: no specs.inc entry or run-time specialisation has equalities, so
-  // their kernels take it as the constant 0 (engine_impl.h neq_of) and hold none of the equality
-  // code; a model with equalities runs the generic kernels (capi.cpp make_capacity).  The block
+  // Joint equalities (two constraint rows each): the eq_* fields of fields.h and their count,
+  // which only the generic kernels read (kSpecHolds, below).  The block
   // is the struct's last 128 bytes: every other member of DModel keeps its offset and the
   // members of Params behind the model keep theirs modulo 128, so the specialised kernels'
   // scalar loads merge and schedule as they did without the block
@@ -122,9 +124,7 @@ struct DModel {
 #undef X_FLT
   int neq;
   // Torsional / rolling friction (contact dimensions 4 and 6), in the same block for the same
-  // reason: no specialisation has such a geom, so their kernels take the largest contact
-  // dimension as the constant 3 (engine_impl.h condim_of) and hold none of the rotational rows'
-  // code, and only the generic kernels (and the reset) touch the torque output.  max_condim is
+  // reason: only the generic kernels (and the reset) touch the torque output.  max_condim is
   // the largest geom_condim of the model; with max_condim > 3 the carves keep five friction
   // coefficients per contact instead of two (carve.h con_mu_width).  contact_torque is
   // [nworld][con_stride][3], the per-sim output beside DData::contact_force (it lives here, in
@@ -178,15 +178,45 @@ namespace mjx {
 
 // Model specialisation: 0 = generic kernels (dims and carves read from Params at run
 // time), k > 0 = kernels compiled for the k-th entry of specs.inc (dims and carves are
-// compile-time constants).  find_spec returns the entry equal to d in every field and in
-// the dof tree (dof_parentid, for the tree-form SPD factors), else 0.
-constexpr int kMaxSpecs = 8;
-int find_spec(const Dims& d, const int* dof_parentid, int ncylinder = 0);
+// compile-time constants).  What selects one is its SpecKey: the dims (capacities included),
+// the candidate pairs with a cylinder geom (kernels compiled with that narrowphase) and the dof
+// tree (dof_parentid, for the tree-form SPD factors).  find_spec returns the entry whose key
+// equals the sim's, else 0.
+struct SpecKey {
+  Dims d;
+  int ncyl;
+  int npar;  // dofs in par: d.nv for a model; an entry with another count matches none
+  int par[kMaxDof];
+};
+inline bool operator==(const SpecKey& a, const SpecKey& b) {
+  static_assert(sizeof(Dims) == 22 * sizeof(int), "Dims is compared as its 22 ints");
+  return memcmp(&a.d, &b.d, sizeof(Dims)) == 0 && a.ncyl == b.ncyl && a.npar == b.npar &&
+         a.npar <= kMaxDof && memcmp(a.par, b.par, sizeof(int) * a.npar) == 0;
+}
+// What every specialisation leaves out: its kernels take these three as constants, so the
+// equality rows of phase A, the torsional / rolling contact rows (contact dimensions 4 and 6)
+// of phases A and C, and the elliptic cone's rows, solver and wrench decode fold away there.
+// A model with any of them runs the generic kernels (capi.cpp make_capacity;
+// mjlab_amd/jit.py ineligible is the same rule in Python).
+struct kSpecHolds {
+  static constexpr int neq = 0, max_condim = 3, cone = 0;
+};
+constexpr bool spec_can_hold(int neq, int max_condim, int cone) {
+  return neq == kSpecHolds::neq && max_condim <= kSpecHolds::max_condim && cone == kSpecHolds::cone;
+}
+int find_spec(const SpecKey& key);
 // Specialisations compiled at run time (jit.hip, loaded by mjx_spec_register) get ids from
 // kRtSpecBase on; find_spec checks them after the compiled specs.inc entries.
 constexpr int kRtSpecBase = 1000;
 using StepFnPtr = void (*)(const struct Params*, int, int, int, int, int, const uint8_t*);
-int register_spec(const Dims& d, const int* par, int npar, StepFnPtr (*fn)(int), int ncylinder = 0);
+int register_spec(const SpecKey& key, StepFnPtr (*fn)(int));
+// What a jit.hip library says of itself (mjx_jit_describe).  The caller sets `size` to its own
+// sizeof(JitInfo); the library answers with its own and fills the rest only when they agree.
+struct JitInfo {
+  int size;
+  unsigned long long hdr;  // csrc/Makefile MJX_HDR_HASH of the headers it was compiled from
+  SpecKey key;
+};
 
 // Explicit actuators (include/mjx355.h mjxActuatorDesc): per-actuator kinds and lag ranges,
 // and the torch-owned per-world buffers, each [nworld, nu] but the ring.

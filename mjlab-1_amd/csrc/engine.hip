@@ -155,22 +155,20 @@ static StepFn generic_fn(int nv, int ph) {
 }
 
 // Model-specialised kernels (spec.hip, one object per specs.inc entry).
-#define MJX_SPEC(id, scene, ...) StepFn spec_fn_##id(int ph);
+#define MJX_SPEC(id, ...) StepFn spec_fn_##id(int ph);
 #include "specs.inc"
 #undef MJX_SPEC
 // Run-time specialisations (jit.hip libraries, mjx_spec_register): ids kRtSpecBase + i.
 struct RtSpec {
-  Dims d;
-  std::vector<int> par;
+  SpecKey key;
   StepFn (*fn)(int);
-  int ncyl;  // cylinder pairs its kernels were compiled for (engine_impl.h SpecCyl)
 };
 static std::vector<RtSpec>& rt_specs() {
   static std::vector<RtSpec> v;
   return v;
 }
-int register_spec(const Dims& d, const int* par, int npar, StepFn (*fn)(int), int ncylinder) {
-  rt_specs().push_back(RtSpec{d, std::vector<int>(par, par + npar), fn, ncylinder});
+int register_spec(const SpecKey& key, StepFn (*fn)(int)) {
+  rt_specs().push_back(RtSpec{key, fn});
   return kRtSpecBase + (int)rt_specs().size() - 1;
 }
 static StepFn spec_fn(int spec, int ph) {
@@ -179,7 +177,7 @@ static StepFn spec_fn(int spec, int ph) {
     return i < (int)rt_specs().size() ? rt_specs()[i].fn(ph) : nullptr;
   }
   switch (spec) {
-#define MJX_SPEC(id, scene, ...) case id: return spec_fn_##id(ph);
+#define MJX_SPEC(id, ...) case id: return spec_fn_##id(ph);
 #include "specs.inc"
 #undef MJX_SPEC
     default: return nullptr;
@@ -244,36 +242,15 @@ static void launch(const Worlds& W, PhaseCode code, int cls, bool with_next_a, h
              arg, W.mask);
 }
 
-int find_spec(const Dims& d, const int* dof_parentid, int ncylinder) {
+int find_spec(const SpecKey& key) {
   if (const char* e = getenv("MJX355_NO_SPEC"))  // diagnostic: force the generic kernels
     if (atoi(e) != 0) return 0;
-  auto eq = [](const Dims& a, const Dims& b) {
-    return a.nq == b.nq && a.nv == b.nv && a.nu == b.nu && a.nbody == b.nbody &&
-           a.njnt == b.njnt && a.ngeom == b.ngeom && a.nsite == b.nsite &&
-           a.nsensor == b.nsensor && a.nsensordata == b.nsensordata && a.npair == b.npair &&
-           a.nhfield == b.nhfield && a.nhfielddata == b.nhfielddata && a.nlevel == b.nlevel &&
-           a.nchild == b.nchild && a.nmocap == b.nmocap && a.ngeom_lds == b.ngeom_lds &&
-           a.npair_all == b.npair_all && a.nstatic == b.nstatic &&
-           a.nstpartner == b.nstpartner && a.nboxbox == b.nboxbox && a.nconmax == b.nconmax && a.njmax == b.njmax;
-  };
-  // and the dof tree of the entry's tree-form SPD factors (rows_chol_tree)
-  auto same_tree = [&](const int* par, int n) {
-    if (n != d.nv) return false;
-    for (int i = 0; i < n; i++)
-      if (dof_parentid[i] != par[i]) return false;
-    return true;
-  };
-  // (a model with cylinder pairs takes only kernels compiled with their narrowphase)
-#define MJX_SPEC(id, scene, ...) \
-  if (eq(d, ModelSpec<id>::dims()) && SpecCyl<id>::n == ncylinder &&       \
-      same_tree(SpecTree<id>::par, SpecTree<id>::npar))                     \
-    return id;
+#define MJX_SPEC(id, ...) \
+  if (key == spec_key<id>()) return id;
 #include "specs.inc"
 #undef MJX_SPEC
-  for (int i = 0; i < (int)rt_specs().size(); i++) {
-    const RtSpec& r = rt_specs()[i];
-    if (eq(d, r.d) && r.ncyl == ncylinder && same_tree(r.par.data(), (int)r.par.size())) return kRtSpecBase + i;
-  }
+  for (int i = 0; i < (int)rt_specs().size(); i++)
+    if (key == rt_specs()[i].key) return kRtSpecBase + i;
   return 0;
 }
 

@@ -1799,101 +1799,7 @@ __device__ __forceinline__ V3 con_frame_torque(const float* S, const int* Si, co
 }
 
 // --------------------------------------------------------------------------- specialisation
-// ModelSpec<SP>: SP > 0 is the SP-th entry of specs.inc (scripts/gen_specs.py); its dims
-// and the three phase carves are returned BY VALUE from constexpr functions, so every
-// d.* bound and L.* LDS offset in the kernel folds to an immediate.  SP = 0 binds the
-// run-time Params copies (generic kernels for any model).
-// the specialisation table: csrc/specs.inc, or (a run-time JIT build, jit.hip) the one entry
-// generated for a model no shipped entry matches
-#ifndef MJX_SPECS_FILE
-#define MJX_SPECS_FILE "specs.inc"
-#endif
-template <int SP> struct ModelSpec {
-  static constexpr bool on = false;
-  static constexpr Dims dims() { return Dims{}; }
-};
-#define MJX_SPEC(id, scene, ...)                                              \
-  template <> struct ModelSpec<id> {                                          \
-    static constexpr bool on = true;                                          \
-    static constexpr Dims dims() { return Dims{__VA_ARGS__}; }                \
-  };
-#include MJX_SPECS_FILE
-#undef MJX_SPEC
-template <int SP> constexpr int spec_nr() { return nr_for_nv(ModelSpec<SP>::dims().nv); }
-// box-box narrowphase compiled in: generic kernels, and specialisations with such pairs
-template <int SP> constexpr bool kBoxBox = SP == 0 || ModelSpec<SP>::dims().nboxbox > 0;
-// cylinder narrowphase compiled in: the generic kernels, and a run-time specialisation of a model
-// with cylinder pairs.  The pair count is not in Dims (its 22-int layout is the JIT libraries'
-// ABI): a generated specs file carries it as MJX_SPEC_CYL(id, pairs), the library exports it
-// (jit.hip mjx_jit_ncyl) and find_spec matches it.  No shipped entry has one, so the shipped
-// specialisations, and a JIT kernel of a cylinder-free model, compile without the code.
-template <int SP> struct SpecCyl { static constexpr int n = 0; };
-#define MJX_SPEC_CYL(id, k)                                                   \
-  template <> struct SpecCyl<id> { static constexpr int n = k; };
-#include MJX_SPECS_FILE
-#undef MJX_SPEC_CYL
-template <int SP> constexpr bool kCylinder = SP == 0 || SpecCyl<SP>::n > 0;
-// at most one contact per lane of the world's wave (every fast carve, nconmax <= 64): the
-// contact loops of phases A and C are then the single lane-per-contact pass; a max carve past
-// 64 contacts (sim.max_capacity: the reference's njmax bounds a world's contacts too) takes
-// the multi-round forms (rank sort, contacts lane + 64 r)
-template <int SP> constexpr bool kCon1 = SP != 0 && ModelSpec<SP>::dims().nconmax <= kWave;
-// (carve index kLdsJG, engine.h Carve: phase B at full capacity with J in global memory)
-template <int SP, int K> struct SpecLds {
-  static constexpr Lds get() {
-    constexpr Lds v = make_lds(ModelSpec<SP>::dims(), K == kLdsJG ? 1 : K, K == kLdsJG);
-    return v;
-  }
-};
-// `const auto& x = dims_of<SP>(P)`: a reference to Params for SP = 0, a constant
-// temporary (folded) for SP > 0.
-template <int SP>
-__device__ __forceinline__ decltype(auto) dims_of(const Params* P) {
-  if constexpr (SP > 0) return ModelSpec<SP>::dims();
-  else return static_cast<const Dims&>(P->d);
-}
-// Joint equalities of the model: none in any specialisation (a constant, so the equality code
-// of phase A folds away there); the generic kernels read the count.
-template <int SP>
-__device__ __forceinline__ int neq_of(const Params* P) {
-  if constexpr (SP > 0) return 0;
-  else return P->m.neq;
-}
-// The model's largest contact dimension: 3 in every specialisation (no specs.inc entry or
-// run-time specialisation has a torsional or rolling contact: capi.cpp make_capacity), so the
-// rotational rows of phases A and C fold away there; the generic kernels read it.
-template <int SP>
-__device__ __forceinline__ int condim_of(const Params* P) {
-  if constexpr (SP > 0) return 3;
-  else return P->m.max_condim;
-}
-// The model's friction cone (Opt::cone, 1 = elliptic): pyramidal in every specialisation (an
-// elliptic model is never specialised: capi.cpp make_capacity), so the cone rows of phase A, the
-// cone solver of phase B and the wrench decode of phase C fold away there.  Wave-uniform.
-template <int SP>
-__device__ __forceinline__ int cone_of(const Params* P) {
-  if constexpr (SP > 0) return 0;
-  else return P->o.cone;
-}
-template <int SP, int K>
-__device__ __forceinline__ decltype(auto) lds_of(const Params* P) {
-  if constexpr (SP > 0) return SpecLds<SP, K>::get();
-  else if constexpr (K == kLdsJG) return static_cast<const Lds&>(P->LPJ);
-  else return static_cast<const Lds&>(P->LP[K]);
-}
-
-// --------------------------------------------------------------------------- tree-sparse SPD
-// A matrix whose pattern is the dof tree's (entry (i, j) != 0 only when one dof is an ancestor
-// of the other: M, the implicit-integration matrix, and the Newton Hessian while every
-// constraint row lies on one root-to-leaf chain) factors WITHOUT fill when children are
-// eliminated before their parents (MuJoCo's L^T D L order).  The tree form of the
-// register-row factor works in the reversed dof order (permuted index c = nvp-1-natural: pads
-// first, leaves before their ancestors), where L[k][j] != 0 (k > j) iff natural(k) is an
-// ancestor of natural(j).  For each 4-column block the trailing columns that block touches
-// are a compile-time bit mask (the union of the block columns' ancestors), so the trailing
-// update skips the structural zeros: 280 instead of 576 FMAs per lane for G1, 100 instead of
-// 160 for Go1.  Skipped terms are exact zeros in the dense sweep, so on the reversed matrix
-// the result equals the dense factor bit for bit.
+// The masks of a dof tree's sparse SPD factor ("tree-sparse SPD", below).
 struct TreeChol {
   bool on;
   uint64_t trail[16];  // per block b: permuted columns k >= 4b+4 with L[k][4b..4b+3] != 0
@@ -1918,30 +1824,110 @@ constexpr TreeChol make_tree_chol(const int* par, int nv) {
   }
   return t;
 }
-template <int SP> struct SpecTree {
-  static constexpr TreeChol get() { return TreeChol{}; }
-  static constexpr int npar = 0;
+// Spec<SP>: SP > 0 is entry SP of the specialisation table: csrc/specs.inc
+// (scripts/gen_specs.py), or (a run-time JIT build, jit.hip) the one entry generated for a
+// model no shipped entry matches.  Its dims, the three phase carves and the tree masks are
+// returned BY VALUE from constexpr functions, so every d.* bound and L.* LDS offset in the
+// kernel folds to an immediate.  SP = 0 binds the run-time Params copies (generic kernels for
+// any model).
+//   role  which carve roles the entry serves (bit 0 fast, bit 1 max / re-solve): kernels of the
+//         other role are not compiled for it (phase_kernel returns null; the generic stand in)
+//   ncyl  candidate pairs with a cylinder geom.  No shipped entry has one, so the shipped
+//         specialisations, and a JIT kernel of a cylinder-free model, compile without the
+//         cylinder narrowphase
+//   par   the dof tree (dof_parentid)
+#ifndef MJX_SPECS_FILE
+#define MJX_SPECS_FILE "specs.inc"
+#endif
+template <int SP> struct Spec {
+  static constexpr bool on = false;
+  static constexpr Dims dims() { return Dims{}; }
+  static constexpr int role = 3, ncyl = 0, npar = 0;
   static constexpr int par[1] = {-1};
+  static constexpr TreeChol tree() { return TreeChol{}; }
 };
-#define MJX_SPEC_TREE(id, ...)                                                \
-  template <> struct SpecTree<id> {                                           \
-    static constexpr int par[] = {__VA_ARGS__};                               \
+#define MJX_SPEC(id, scene, role_, ncyl_, dims_, par_)                        \
+  template <> struct Spec<id> {                                               \
+    static constexpr bool on = true;                                          \
+    static constexpr Dims dims() { return Dims{MJX_UNPAREN(dims_)}; }         \
+    static constexpr int role = role_, ncyl = ncyl_;                          \
+    static constexpr int par[] = {MJX_UNPAREN(par_)};                         \
     static constexpr int npar = sizeof(par) / sizeof(int);                    \
-    static constexpr TreeChol get() { return make_tree_chol(par, npar); }     \
+    static constexpr TreeChol tree() { return make_tree_chol(par, npar); }    \
   };
 #include MJX_SPECS_FILE
-#undef MJX_SPEC_TREE
-// which carve roles a specialisation serves (bit 0 fast, bit 1 max / re-solve): kernels of
-// the other role are not compiled for it (phase_kernel returns null; the generic stand in)
-template <int SP> struct SpecRole { static constexpr int mask = 3; };
-#define MJX_SPEC_ROLE(id, m)                                                  \
-  template <> struct SpecRole<id> { static constexpr int mask = m; };
-#include MJX_SPECS_FILE
-#undef MJX_SPEC_ROLE
+#undef MJX_SPEC
+// what selects entry SP (engine.h SpecKey; a tree past kMaxDof is cut: mjx_spec_register refuses it)
+template <int SP> SpecKey spec_key() {
+  SpecKey k{Spec<SP>::dims(), Spec<SP>::ncyl, Spec<SP>::npar, {}};
+  for (int i = 0; i < k.npar && i < kMaxDof; i++) k.par[i] = Spec<SP>::par[i];
+  return k;
+}
+template <int SP> constexpr int spec_nr() { return nr_for_nv(Spec<SP>::dims().nv); }
+// box-box narrowphase compiled in: generic kernels, and specialisations with such pairs
+template <int SP> constexpr bool kBoxBox = SP == 0 || Spec<SP>::dims().nboxbox > 0;
+// cylinder narrowphase compiled in: the generic kernels, and a run-time specialisation of a model
+// with cylinder pairs
+template <int SP> constexpr bool kCylinder = SP == 0 || Spec<SP>::ncyl > 0;
+// at most one contact per lane of the world's wave (every fast carve, nconmax <= 64): the
+// contact loops of phases A and C are then the single lane-per-contact pass; a max carve past
+// 64 contacts (sim.max_capacity: the reference's njmax bounds a world's contacts too) takes
+// the multi-round forms (rank sort, contacts lane + 64 r)
+template <int SP> constexpr bool kCon1 = SP != 0 && Spec<SP>::dims().nconmax <= kWave;
 // the tree form is compiled for a specialisation whose dof tree is known and matches its nv
 template <int SP> constexpr bool kTree =
-    SP > 0 && SpecTree<SP>::npar == ModelSpec<SP>::dims().nv && SpecTree<SP>::get().on;
+    SP > 0 && Spec<SP>::npar == Spec<SP>::dims().nv && Spec<SP>::tree().on;
+// (carve index kLdsJG, engine.h Carve: phase B at full capacity with J in global memory)
+template <int SP, int K> struct SpecLds {
+  static constexpr Lds get() {
+    constexpr Lds v = make_lds(Spec<SP>::dims(), K == kLdsJG ? 1 : K, K == kLdsJG);
+    return v;
+  }
+};
+// `const auto& x = dims_of<SP>(P)`: a reference to Params for SP = 0, a constant
+// temporary (folded) for SP > 0.
+template <int SP>
+__device__ __forceinline__ decltype(auto) dims_of(const Params* P) {
+  if constexpr (SP > 0) return Spec<SP>::dims();
+  else return static_cast<const Dims&>(P->d);
+}
+// The model's equality count, largest contact dimension and friction cone (Opt::cone, 1 =
+// elliptic; wave-uniform): the constants of engine.h kSpecHolds in a specialised kernel, read
+// by the generic ones.
+template <int SP>
+__device__ __forceinline__ int neq_of(const Params* P) {
+  if constexpr (SP > 0) return kSpecHolds::neq;
+  else return P->m.neq;
+}
+template <int SP>
+__device__ __forceinline__ int condim_of(const Params* P) {
+  if constexpr (SP > 0) return kSpecHolds::max_condim;
+  else return P->m.max_condim;
+}
+template <int SP>
+__device__ __forceinline__ int cone_of(const Params* P) {
+  if constexpr (SP > 0) return kSpecHolds::cone;
+  else return P->o.cone;
+}
+template <int SP, int K>
+__device__ __forceinline__ decltype(auto) lds_of(const Params* P) {
+  if constexpr (SP > 0) return SpecLds<SP, K>::get();
+  else if constexpr (K == kLdsJG) return static_cast<const Lds&>(P->LPJ);
+  else return static_cast<const Lds&>(P->LP[K]);
+}
 
+// --------------------------------------------------------------------------- tree-sparse SPD
+// A matrix whose pattern is the dof tree's (entry (i, j) != 0 only when one dof is an ancestor
+// of the other: M, the implicit-integration matrix, and the Newton Hessian while every
+// constraint row lies on one root-to-leaf chain) factors WITHOUT fill when children are
+// eliminated before their parents (MuJoCo's L^T D L order).  The tree form of the
+// register-row factor works in the reversed dof order (permuted index c = nvp-1-natural: pads
+// first, leaves before their ancestors), where L[k][j] != 0 (k > j) iff natural(k) is an
+// ancestor of natural(j).  For each 4-column block the trailing columns that block touches
+// are a compile-time bit mask (the union of the block columns' ancestors), so the trailing
+// update skips the structural zeros: 280 instead of 576 FMAs per lane for G1, 100 instead of
+// 160 for Go1.  Skipped terms are exact zeros in the dense sweep, so on the reversed matrix
+// the result equals the dense factor bit for bit.  (The masks: TreeChol, above.)
 // Register rows of the reversed matrix: lane i holds row nvp-1-i of Mm (row stride nvp, the
 // natural order), columns reversed; lanes >= nvp identity.  The reversed lower triangle is
 // the natural UPPER one: Mm must hold the full symmetric matrix (tiles_store_sym).
@@ -1967,8 +1953,8 @@ __device__ __forceinline__ void rows_load_rev(float (&A)[NR], const float* Mm, i
 template <int NR, int SP, int J0>
 __device__ __forceinline__ void rows_chol_tree_blk(float (&A)[NR], float& rdiag, float* cb, int lane) {
   if constexpr (J0 < NR) {
-    constexpr uint32_t ib = J0 < 64 ? SpecTree<SP>::get().inblk[J0 >> 2] : 0u;
-    constexpr uint64_t tr = J0 < 64 ? SpecTree<SP>::get().trail[J0 >> 2] : 0ull;
+    constexpr uint32_t ib = J0 < 64 ? Spec<SP>::tree().inblk[J0 >> 2] : 0u;
+    constexpr uint64_t tr = J0 < 64 ? Spec<SP>::tree().trail[J0 >> 2] : 0ull;
     const int ln = opaque_lane(lane);
 #pragma unroll
     for (int t = 0; t < 4; t++) {
@@ -2540,7 +2526,7 @@ constexpr bool lean_spec() {
   if constexpr (SP <= 0) {
     return false;
   } else {
-    constexpr Dims d = ModelSpec<SP>::dims();
+    constexpr Dims d = Spec<SP>::dims();
     return nr_for_nv(d.nv) <= 20 && d.nstatic == 0 && d.nboxbox == 0 &&
            make_lds(d, 0).total * 4 <= 10240 && make_lds(d, 1).total * 4 <= 10240 &&
            make_lds(d, 2).total * 4 <= 10240;
@@ -5466,7 +5452,7 @@ using StepFn = void (*)(const Params*, int, int, int, int, int, const uint8_t*);
 // kernel of phase code ph (engine.h PhaseCode); null where the specialisation's role has none
 template <int NR, int SP>
 StepFn phase_kernel(int ph) {
-  constexpr int role = SpecRole<SP>::mask;
+  constexpr int role = Spec<SP>::role;
   // the variants whose phases A and C run the actuator networks: generic kernels only (they stand
   // in for a specialisation's, as for every role a specialisation lacks)
   if (ph & kPhNet) {

@@ -24,10 +24,17 @@ struct ModelTables {
   int nmaskword = 0;
   int neq = 0;     // joint equalities (fields.h counts the eq_* fields by it)
   int max_condim = 3;  // largest geom_condim, at least 3 (check_condims; engine.h DModel::max_condim)
-  int ncylinder = 0;  // candidate pairs with a cylinder: such a model runs the generic kernels
-                      // (engine_impl.h kCylinder; not in Dims, whose layout the JIT ABI fixes)
+  int ncylinder = 0;  // candidate pairs with a cylinder geom
   int ncsens = 0;  // 0 past 64 single-slot contact sensors (phase C then matches serially)
-  std::vector<int32_t> dof_parentid;  // as given: find_spec checks a specialisation's dof tree
+  std::vector<int32_t> dof_parentid;  // as given
+  // what selects the specialised kernels of a sim of this model at a capacity (engine.h SpecKey)
+  SpecKey spec_key(int nconmax, int njmax) const {
+    SpecKey k{d, ncylinder, (int)dof_parentid.size(), {}};
+    k.d.nconmax = nconmax;
+    k.d.njmax = njmax;
+    std::copy(dof_parentid.begin(), dof_parentid.end(), k.par);  // nv <= kMaxDof (check_limits)
+    return k;
+  }
   // engine.h DModel, the host-derived part
   std::vector<uint64_t> dof_ancmask, body_submask, body_dofmask;
   std::vector<int32_t> body_rec, dof_rec, act_rec;

@@ -13,7 +13,7 @@ namespace mjx {
 #define MJX_CAT(a, b) MJX_CAT2(a, b)
 StepFn MJX_CAT(spec_fn_, MJX_SPEC_ID)(int ph) {
   constexpr int NR = spec_nr<MJX_SPEC_ID>();
-  static_assert(ModelSpec<MJX_SPEC_ID>::on, "unknown specialisation");
+  static_assert(Spec<MJX_SPEC_ID>::on, "unknown specialisation");
   // ph 3: the latency form of phase B (full-capacity row class, masked forward); 4-6: the
   // overflow re-solve's A / B / C (phase_kernel)
   return phase_kernel<NR, MJX_SPEC_ID>(ph);

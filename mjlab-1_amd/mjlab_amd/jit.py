@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
 import subprocess
 import tempfile
 
@@ -78,7 +79,7 @@ def spec_dims(m) -> dict:
 def cylinder_pairs(m) -> int:
   """Candidate pairs of the compiled model with a cylinder geom (type 5): what
   csrc/model_tables.h counts as ModelTables::ncylinder.  Kernels specialised for such a model
-  are compiled with the cylinder narrowphase (the MJX_SPEC_CYL line of its specs file)."""
+  are compiled with the cylinder narrowphase (the ncyl of its specs-file entry)."""
   a = m.arrays
   gt = np.asarray(a.get("geom_type", ())).reshape(-1)
   p1, p2 = (np.asarray(a.get(k, ()), dtype=np.int64).reshape(-1) for k in ("pair_geom1", "pair_geom2"))
@@ -89,34 +90,29 @@ def dof_tree(m) -> tuple:
   return tuple(int(p) for p in np.asarray(m.dof_parentid).reshape(-1))
 
 
-# a specs file is included once per macro (MJX_SPEC, MJX_SPEC_TREE, MJX_SPEC_ROLE); the others
-# default to nothing for that pass
-GUARD_HEAD = ["#ifndef MJX_SPEC", "#define MJX_SPEC(...)", "#define MJX_SPEC_DEFAULTED", "#endif",
-              "#ifndef MJX_SPEC_TREE", "#define MJX_SPEC_TREE(...)", "#define MJX_SPEC_TREE_DEFAULTED",
-              "#endif",
-              "// MJX_SPEC_ROLE(id, mask): 1 = a fast carve, 2 = a max (re-solve) carve; the kernels",
-              "// only one role launches are left out of that entry (the generic ones stand in)",
-              "#ifndef MJX_SPEC_ROLE", "#define MJX_SPEC_ROLE(...)", "#define MJX_SPEC_ROLE_DEFAULTED",
-              "#endif",
-              "// MJX_SPEC_CYL(id, pairs): candidate pairs with a cylinder geom (kernels with its narrowphase)",
-              "#ifndef MJX_SPEC_CYL", "#define MJX_SPEC_CYL(...)", "#define MJX_SPEC_CYL_DEFAULTED", "#endif"]
-GUARD_TAIL = ["#ifdef MJX_SPEC_DEFAULTED", "#undef MJX_SPEC", "#undef MJX_SPEC_DEFAULTED", "#endif",
-              "#ifdef MJX_SPEC_TREE_DEFAULTED", "#undef MJX_SPEC_TREE", "#undef MJX_SPEC_TREE_DEFAULTED",
-              "#endif",
-              "#ifdef MJX_SPEC_ROLE_DEFAULTED", "#undef MJX_SPEC_ROLE", "#undef MJX_SPEC_ROLE_DEFAULTED",
-              "#endif",
-              "#ifdef MJX_SPEC_CYL_DEFAULTED", "#undef MJX_SPEC_CYL", "#undef MJX_SPEC_CYL_DEFAULTED", "#endif"]
+# A specs file (csrc/specs.inc, or the one-entry file of a run-time build) is this comment and
+# one MJX_SPEC line per entry; every includer defines the macro and picks what it needs.
+SPECS_HEADER = ["// MJX_SPEC(id, scene, role, ncyl, (" + ", ".join(ORDER) + "), (dof_parentid...))",
+                "// role: 1 = a fast carve, 2 = a max (re-solve) carve, 3 = both; the kernels only one",
+                "//   role launches are left out of that entry (the generic ones stand in)",
+                "// ncyl: candidate pairs with a cylinder geom (> 0: kernels with its narrowphase)",
+                "// dof_parentid: the dof tree (tree-sparse SPD factors)"]
 
 
-def entry_lines(sid: int, name: str, dims: dict, par: tuple, role: int | None = None,
-                ncyl: int = 0) -> list[str]:
-  """One specs.inc entry (scripts/gen_specs.py writes the shipped table from the same)."""
-  out = [f"MJX_SPEC({sid}, {name}, " + ", ".join(str(int(dims[k])) for k in ORDER) + ")",
-         f"MJX_SPEC_TREE({sid}, " + ", ".join(str(p) for p in par) + ")"]
-  if role is not None:
-    out.append(f"MJX_SPEC_ROLE({sid}, {role})")
-  if ncyl > 0:
-    out.append(f"MJX_SPEC_CYL({sid}, {ncyl})")
+def spec_line(sid: int, name: str, role: int, ncyl: int, dims: dict, par: tuple) -> str:
+  """One specs-file entry (scripts/gen_specs.py writes the shipped table from the same)."""
+  return (f"MJX_SPEC({sid}, {name}, {role}, {ncyl}, (" + ", ".join(str(int(dims[k])) for k in ORDER)
+          + "), (" + ", ".join(str(int(p)) for p in par) + "))")
+
+
+def parse_specs(text: str) -> list[dict]:
+  """The entries of a specs file: id, scene, role, ncyl, dims (by ORDER) and par."""
+  out = []
+  for m in re.finditer(r"^MJX_SPEC\((\d+), (\w+), (\d+), (\d+), \(([^)]*)\), \(([^)]*)\)\)$", text, re.M):
+    dims = [int(v) for v in m.group(5).split(",")]
+    assert len(dims) == len(ORDER), m.group(0)
+    out.append(dict(id=int(m.group(1)), scene=m.group(2), role=int(m.group(3)), ncyl=int(m.group(4)),
+                    dims=dict(zip(ORDER, dims)), par=tuple(int(v) for v in m.group(6).split(","))))
   return out
 
 
@@ -150,12 +146,28 @@ def library_path(model, nconmax: int, njmax: int, role: int) -> tuple[str, str, 
   d["nconmax"], d["njmax"] = int(nconmax), int(njmax)
   par = dof_tree(model)
   ncyl = cylinder_pairs(model)
-  body = "\n".join(entry_lines(0, "jit", d, par, role, ncyl))
-  key = hashlib.sha1((body + _source_hash()).encode()).hexdigest()[:20]
+  key = hashlib.sha1((spec_line(0, "jit", role, ncyl, d, par) + _source_hash()).encode()).hexdigest()[:20]
   # an entry id of its own (template instantiations named apart from every other library's)
   sid = 2000 + int(key[:6], 16) % 900000
-  text = "\n".join(GUARD_HEAD + entry_lines(sid, "jit", d, par, role, ncyl) + GUARD_TAIL) + "\n"
+  text = "\n".join(SPECS_HEADER + [spec_line(sid, "jit", role, ncyl, d, par)]) + "\n"
   return os.path.join(CACHE, f"spec_{key}.so"), text, sid
+
+
+def ineligible(model) -> str | None:
+  """Why no specialised kernel can run `model` (None: one can).  The rule of csrc/engine.h
+  spec_can_hold: specialised kernels hold no equality rows, no torsional or rolling contact rows
+  and no elliptic cone, so such a model runs the generic kernels only."""
+  if len(model.arrays.get("eq_type", ())) > 0:
+    return "a model with equality constraints runs the generic kernels only " \
+           "(equalities are not compiled into specialised or JIT kernels)"
+  cd = np.asarray(model.arrays.get("geom_condim", ())).reshape(-1)
+  if cd.size and int(cd.max()) > 3:
+    return "a model with torsional or rolling contacts (condim 4 or 6) runs the generic kernels " \
+           "only (their rows are not compiled into specialised or JIT kernels)"
+  if int(getattr(model, "cone", 0)) != 0:
+    return "a model with elliptic friction cones runs the generic kernels only " \
+           "(the cone rows and solver are not compiled into specialised or JIT kernels)"
+  return None
 
 
 def _user_cache() -> str:
@@ -190,20 +202,15 @@ def _local_rank() -> int:
 def ensure_library(model, nconmax: int, njmax: int, role: int, compile_ok: bool = True,
                    wait_s: float = 900.0) -> str | None:
   """The cached library for this model and capacity, compiled first if `compile_ok` (None when
-  it is absent and may not be built, or hipcc is missing).
+  the model is `ineligible`, or the library is absent and may not be built, or hipcc is missing).
 
-  One process per GPU builds each key once: the compile runs under an exclusive lock file
-  next to the library, so ranks that ask for the same key at once wait for the first one's
-  result instead of compiling it again (and a rank that is not local rank 0 only waits, up to
-  `wait_s`).  The library goes to the in-tree cache, or to ~/.cache/mjlab_amd/jit_cache when
-  the package directory is read-only.  Raises RuntimeError when hipcc fails, OSError when no
-  cache directory can be written."""
-  # torsional / rolling contact rows (condim 4 or 6) exist only in the generic kernels: such a
-  # model is never specialised (the engine would not select the library either)
-  cd = np.asarray(model.arrays.get("geom_condim", ())).reshape(-1)
-  if cd.size and int(cd.max()) > 3:
-    return None
-  if int(getattr(model, "cone", 0)) != 0:  # likewise the elliptic cone's rows and solver
+  Each key is built once: the compile runs under an exclusive lock file next to the library, so
+  ranks that ask for the same key at once wait for the result of whichever got the lock first
+  instead of compiling it again (local rank 0 blocks on the lock; the others poll it, up to
+  `wait_s`, so that a crash of the compiling rank does not hang them).  The library goes to the
+  in-tree cache, or to ~/.cache/mjlab_amd/jit_cache when the package directory is read-only.
+  Raises RuntimeError when hipcc fails, OSError when no cache directory can be written."""
+  if ineligible(model) is not None:  # the engine would not select the library either
     return None
   path, text, sid = library_path(model, nconmax, njmax, role)
   hit = _lookup(path)
@@ -216,36 +223,37 @@ def ensure_library(model, nconmax: int, njmax: int, role: int, compile_ok: bool 
   cache = _writable_cache()
   path = os.path.join(cache, os.path.basename(path))
   with open(path + ".lock", "w") as lock:
-    if _local_rank() != 0:
-      # another local rank compiles; poll its lock so a crash there does not hang this one
-      t0 = time.monotonic()
-      while True:
-        try:
-          fcntl.flock(lock, fcntl.LOCK_EX | fcntl.LOCK_NB)
-          break
-        except BlockingIOError:
-          if time.monotonic() - t0 > wait_s:
-            raise RuntimeError(f"mjlab_amd.jit: timed out waiting for {path}")
-          time.sleep(1.0)
-    else:
-      fcntl.flock(lock, fcntl.LOCK_EX)
-    if os.path.exists(path):  # built while this process waited
-      return path
-    with tempfile.TemporaryDirectory(dir=cache) as tmp:
-      inc = os.path.join(tmp, "jit_specs.inc")
-      with open(inc, "w") as fh:
-        fh.write(text)
-      out = os.path.join(tmp, "lib.so")
-      cmd = [HIPCC, *FLAGS, f"-I{CSRC}", f'-DMJX_SPECS_FILE="{inc}"', f"-DMJX_JIT_ID={sid}",
-             f"-DMJX_HDR_HASH=0x{header_hash()}ULL", os.path.join(CSRC, "jit.hip"), "-o", out]
-      r = subprocess.run(cmd, capture_output=True, text=True)
-      if r.returncode != 0:
-        raise RuntimeError(f"mjlab_amd.jit: hipcc failed for {path}:\n{r.stderr[-4000:]}")
-      os.replace(out, path)  # atomic: a concurrent reader sees the whole library or none
-    try:  # a waiter holding the lock finds the library once it gets the lock
-      os.unlink(path + ".lock")
-    except OSError:
-      pass
+    try:
+      if _local_rank() != 0:
+        t0 = time.monotonic()
+        while True:
+          try:
+            fcntl.flock(lock, fcntl.LOCK_EX | fcntl.LOCK_NB)
+            break
+          except BlockingIOError:
+            if time.monotonic() - t0 > wait_s:
+              raise RuntimeError(f"mjlab_amd.jit: timed out waiting for {path}")
+            time.sleep(1.0)
+      else:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+      if os.path.exists(path):  # built while this process waited
+        return path
+      with tempfile.TemporaryDirectory(dir=cache) as tmp:
+        inc = os.path.join(tmp, "jit_specs.inc")
+        with open(inc, "w") as fh:
+          fh.write(text)
+        out = os.path.join(tmp, "lib.so")
+        cmd = [HIPCC, *FLAGS, f"-I{CSRC}", f'-DMJX_SPECS_FILE="{inc}"', f"-DMJX_JIT_ID={sid}",
+               f"-DMJX_HDR_HASH=0x{header_hash()}ULL", os.path.join(CSRC, "jit.hip"), "-o", out]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+          raise RuntimeError(f"mjlab_amd.jit: hipcc failed for {path}:\n{r.stderr[-4000:]}")
+        os.replace(out, path)  # atomic: a concurrent reader sees the whole library or none
+    finally:  # (a waiter that holds the open lock file still gets the lock, and finds the library)
+      try:
+        os.unlink(path + ".lock")
+      except OSError:
+        pass
   return path
 
 

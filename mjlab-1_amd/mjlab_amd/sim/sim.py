@@ -326,18 +326,11 @@ class Simulation:
     self.num_envs = int(num_envs)
     self.line_search = "exact"  # whatever cfg.ls_parallel says (see SimulationCfg.ls_parallel)
     self._default_model_fields: dict[str, torch.Tensor] = {}
-    if cfg.specialize == "always" and _neq(model) > 0:
-      raise NotImplementedError(
-          "specialize='always': a model with equality constraints runs the generic kernels only "
-          "(equalities are not compiled into specialised or JIT kernels)")
-    if cfg.specialize == "always" and _max_condim(model) > 3:
-      raise NotImplementedError(
-          "specialize='always': a model with torsional or rolling contacts (condim 4 or 6) runs "
-          "the generic kernels only (their rows are not compiled into specialised or JIT kernels)")
-    if cfg.specialize == "always" and int(getattr(model, "cone", 0)) != 0:
-      raise NotImplementedError(
-          "specialize='always': a model with elliptic friction cones runs the generic kernels "
-          "only (the cone rows and solver are not compiled into specialised or JIT kernels)")
+    if cfg.specialize == "always":
+      from .. import jit
+      why = jit.ineligible(model)
+      if why is not None:
+        raise NotImplementedError(f"specialize='always': {why}")
     dev = torch.device(device)
     if dev.type != "cuda":
       raise MjxError("mjlab_amd.Simulation runs only on a ROCm GPU (device 'cuda:N'); "
@@ -617,18 +610,9 @@ class Simulation:
     env = os.environ.get("MJX355_JIT")
     if env is not None:
       policy = "always" if env != "0" else "never"
-    if _max_condim(model) > 3 or int(getattr(model, "cone", 0)) != 0:
-      # likewise the rotational contact rows (csrc/engine_impl.h condim_of) and the elliptic
-      # cone's rows and solver (cone_of)
-      return False
-    if _neq(model) > 0:
-      # equality rows exist only in the generic kernels (csrc/engine_impl.h neq_of): a
-      # specialisation is neither looked up nor compiled, and jit.spec_dims never asked
-      # (specialize="always" was refused when the Simulation was created)
-      return False
-    if policy == "never" or os.environ.get("MJX355_NO_SPEC"):
-      return False
     from .. import jit
+    if policy == "never" or os.environ.get("MJX355_NO_SPEC") or jit.ineligible(model) is not None:
+      return False
     want = []
     if info["spec"] == 0:
       want.append((info["nconmax"], info["njmax"], 1))

@@ -13,11 +13,11 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mjlab-1_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function",
          "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-DMJX_HDR_HASH=0x1ULL"]
-names = {}
-for line in open(os.path.join(CSRC, "specs.inc")):
-  m = re.match(r"MJX_SPEC\((\d+), (\w+),.*, (\d+), (\d+)\)$", line.strip())
-  if m:
-    names[m.group(1)] = f"{m.group(2)} {m.group(3)}/{m.group(4)}"
+sys.path.insert(0, os.path.join(CSRC, ".."))
+from mjlab_amd.jit import parse_specs  # noqa: E402
+
+names = {str(e["id"]): f"{e['scene']} {e['dims']['nconmax']}/{e['dims']['njmax']}"
+         for e in parse_specs(open(os.path.join(CSRC, "specs.inc")).read())}
 
 
 def resources(target):

@@ -299,9 +299,9 @@ int main(int argc, char** argv) {
   if (argc > 1 && !strcmp(argv[1], "select")) return print_selection();
   check_known();
   // every compiled specialisation, with every class capacity below its row capacity
-#define MJX_SPEC(id, scene, ...)                                  \
+#define MJX_SPEC(id, scene, role, ncyl, dims, par)                \
   {                                                               \
-    const Dims d{__VA_ARGS__};                                    \
+    const Dims d{MJX_UNPAREN(dims)};                              \
     std::vector<int> caps;                                        \
     for (int c = 1; c < d.njmax; c++) caps.push_back(c);          \
     check_b(d, caps);                                             \

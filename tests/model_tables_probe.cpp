@@ -29,8 +29,10 @@ const char* mt_build(const mjxModelDesc* desc) {
 long mt_table(const char* name, void* out, long cap) {
   const mjx::ModelTables& t = g_tables;
   const int scalars[2] = {t.nmaskword, t.ncsens};
+  const mjx::SpecKey key = t.spec_key(0, 0);  // Dims, ncyl, npar, par[64] as ints
   const std::map<std::string, std::pair<const void*, size_t>> all = {
       {"dims", {&t.d, sizeof(t.d)}}, {"scalars", {scalars, sizeof(scalars)}},
+      {"spec_key", {&key, sizeof(key)}},
       {"dof_parentid", span(t.dof_parentid)}, {"dof_ancmask", span(t.dof_ancmask)},
       {"body_submask", span(t.body_submask)}, {"body_dofmask", span(t.body_dofmask)},
       {"body_rec", span(t.body_rec)}, {"dof_rec", span(t.dof_rec)}, {"act_rec", span(t.act_rec)},

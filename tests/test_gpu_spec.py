@@ -28,6 +28,19 @@ def test_shipped_tasks_use_specialised_kernels(task, gpu_device):
   assert _spec(env.sim) > 0, f"{task} fell back to the generic kernels (regenerate specs.inc)"
 
 
+@pytest.mark.parametrize("fast,entry", [((16, 64), 2), ((48, 160), 8)])
+def test_capacities_select_their_table_entries(fast, entry, gpu_device):
+  """csrc/specs.inc: go1_velocity is entry 2 at (16, 64), entry 8 at (48, 160) (both role 1, a
+  fast carve) and entry 12 at the max capacity (300, 300) (role 2)."""
+  from mjlab_amd.scenes import load_scene
+  from mjlab_amd.sim import Simulation, SimulationCfg
+  sim = Simulation(8, SimulationCfg(engine_capacity=fast, njmax=300), load_scene("go1_velocity"), gpu_device)
+  info = sim.info()
+  assert (info["nconmax"], info["njmax"]) == fast and (info["nconmax_max"], info["njmax_max"]) == (300, 300)
+  assert info["spec"] == entry == _spec(sim)
+  assert info["spec_max"] == 12
+
+
 def _make_sim(scene, n, generic):
   from mjlab_amd.scenes import load_scene
   from mjlab_amd.sim import MujocoCfg, Simulation, SimulationCfg

@@ -2,7 +2,7 @@
 other kernel headers than libmjx355.so.  Its kernels would read the launch parameters (Params,
 the LDS carves, the data arena) through another struct layout -- round 6 saw exactly that
 fault the device once, when a JIT library was compiled from headers edited after the last
-engine build.  Here a stand-in library exports the five jit.hip entry points with a wrong
+engine build.  Here a stand-in library exports the two jit.hip entry points with a wrong
 header hash; registering it must fail with an error, before any kernel could be launched."""
 
 import ctypes
@@ -15,11 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "mjlab-1_amd", "mjlab_amd", "libmjx355.so")
 
 FAKE = r"""
-typedef struct { int v[22]; } Dims;  /* mjx::Dims: 22 ints (csrc/engine.h) */
-int mjx_jit_abi(void) { return (int)sizeof(Dims); }
-unsigned long long mjx_jit_hdr(void) { return HDR; }
-void mjx_jit_dims(Dims* out) { for (int i = 0; i < 22; i++) out->v[i] = 1; }
-int mjx_jit_tree(int* par, int cap) { if (cap > 0) par[0] = -1; return 1; }
+/* mjx::JitInfo (csrc/engine.h): size, header hash, SpecKey {Dims: 22 ints, ncyl, npar, par[64]} */
+typedef struct { int size; unsigned long long hdr; int dims[22]; int ncyl, npar, par[64]; } JitInfo;
+void mjx_jit_describe(JitInfo* out) {
+  int same = out->size == (int)sizeof(JitInfo);
+  out->size = (int)sizeof(JitInfo);
+  if (!same) return;
+  SET_HDR
+  for (int i = 0; i < 22; i++) out->dims[i] = 1;
+  out->ncyl = 0; out->npar = 1; out->par[0] = -1;
+}
 void* mjx_jit_kernel(int ph) { (void)ph; return 0; }
 """
 
@@ -37,7 +42,7 @@ def _fake(tmp_path, hdr: str, name: str) -> str:
   src = tmp_path / f"{name}.c"
   src.write_text(FAKE)
   out = tmp_path / f"{name}.so"
-  r = subprocess.run(["gcc", "-shared", "-fPIC", f"-DHDR={hdr}", "-o", str(out), str(src)],
+  r = subprocess.run(["gcc", "-shared", "-fPIC", f"-DSET_HDR=out->hdr = {hdr};", "-o", str(out), str(src)],
                      capture_output=True, text=True)
   if r.returncode != 0:
     pytest.skip(f"gcc unavailable: {r.stderr[-200:]}")
@@ -64,10 +69,9 @@ def test_stale_jit_library_is_refused(lib, tmp_path):
 
 
 def test_library_without_the_hash_is_refused(lib, tmp_path):
-  src = FAKE.replace("unsigned long long mjx_jit_hdr(void) { return HDR; }", "")
-  (tmp_path / "nohdr.c").write_text(src)
+  (tmp_path / "nohdr.c").write_text(FAKE)
   out = tmp_path / "nohdr.so"
-  r = subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(out), str(tmp_path / "nohdr.c")],
+  r = subprocess.run(["gcc", "-shared", "-fPIC", "-DSET_HDR=", "-o", str(out), str(tmp_path / "nohdr.c")],
                      capture_output=True, text=True)
   if r.returncode != 0:
     pytest.skip("gcc unavailable")

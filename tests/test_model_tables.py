@@ -44,7 +44,7 @@ GEOM_HFIELD, GEOM_BOX, SENS_CONTACT = 1, 6, 4  # csrc/engine.h
 K_BODY_REC, K_DOF_REC, K_ACT_REC, K_STATIC_CHUNK = 20, 12, 4, 64
 DIMS = ("nq nv nu nbody njnt ngeom nsite nsensor nsensordata npair nhfield nhfielddata nlevel nchild "
         "nmocap ngeom_lds npair_all nstatic nstpartner nboxbox nconmax njmax").split()
-DTYPES = {"dims": np.int32, "scalars": np.int32, "dof_parentid": np.int32, "dof_ancmask": np.uint64,
+DTYPES = {"dims": np.int32, "scalars": np.int32, "spec_key": np.int32, "dof_parentid": np.int32, "dof_ancmask": np.uint64,
           "body_submask": np.uint64, "body_dofmask": np.uint64, "body_rec": np.int32, "dof_rec": np.int32,
           "act_rec": np.int32, "geom_lds": np.int32, "lds_geom": np.int32, "st_geom": np.int32,
           "st_pairadr": np.int32, "st_partner": np.int32, "st_aabb": np.float32,
@@ -82,6 +82,9 @@ def _model(case):
   kind, name = case.split(":")
   if kind == "zoo":
     return zoo.get(name).model
+  if kind == "cyl":  # the cylinder-pair scenes of tests/test_gpu_cylinder_pairs.py
+    import test_gpu_cylinder_pairs as cyl
+    return cyl.model(name)
   from mjlab_amd.scenes import load_scene
   return load_scene(name)
 
@@ -138,6 +141,41 @@ def _lo_hi(mask64):
 
 def _i32(words):
   return np.asarray(words, np.uint32).view(np.int32)
+
+
+# ----------------------------------------------------------------------------- the specialisation key
+# mjlab_amd.jit derives in numpy what selects a model's specialised kernels (engine.h SpecKey);
+# the engine derives it in build_model_tables and is the authority.  A difference would only cost
+# speed (find_spec falls back to the generic kernels), so nothing else would show it.  The
+# shipped rough scenes have the static terrain tail and the box-box pairs; the two cylinder
+# scenes have cylinder pairs, one of them against a terrain box.
+KEY_CASES = CASES + ("cyl:capsule", "cyl:terrain_box")
+
+
+@pytest.mark.parametrize("case", KEY_CASES)
+def test_spec_key_equals_the_python_derivation(probe, case):
+  from mjlab_amd import jit
+  m, a, t, nmaskword = _tables(probe, case)
+  key = t["spec_key"].tolist()
+  assert len(key) == len(DIMS) + 2 + 64
+  dims, (ncyl, npar), par = dict(zip(DIMS, key)), key[len(DIMS):len(DIMS) + 2], key[len(DIMS) + 2:]
+  want = jit.spec_dims(m)
+  assert list(want) == DIMS == jit.ORDER
+  for n in DIMS:
+    if n not in ("nconmax", "njmax"):
+      assert dims[n] == want[n], n
+  assert dims == t["d"]
+  assert ncyl == jit.cylinder_pairs(m)
+  assert tuple(par[:npar]) == jit.dof_tree(m) and npar == m.nv
+
+
+def test_spec_key_cases_cover_the_tail_boxes_and_cylinders(probe):
+  seen = {n: 0 for n in ("nstatic", "nstpartner", "nboxbox", "ncyl")}
+  for case in KEY_CASES:
+    t = _tables(probe, case)[2]
+    for n in seen:
+      seen[n] = max(seen[n], t["d"][n] if n != "ncyl" else int(t["spec_key"][len(DIMS)]))
+  assert all(v > 0 for v in seen.values()), seen
 
 
 # ----------------------------------------------------------------------------- dims

@@ -4,7 +4,6 @@ the tracking task's 56 / 200 fast carve under the reference's njmax (250 rows,
 (specs.inc) carrying the same capacities, so the bench configs never fall back to the
 generic kernels."""
 import os
-import re
 
 import pytest
 
@@ -57,9 +56,10 @@ def test_max_capacity_is_the_resolve_carve(monkeypatch):
 
 def test_specs_carry_the_task_capacities():
   text = open(os.path.join(ROOT, "mjlab-1_amd", "csrc", "specs.inc")).read()
+  from mjlab_amd import jit
   caps = {}
-  for mm in re.finditer(r"^MJX_SPEC\(\d+, (\w+),.*, (\d+), (\d+)\)$", text, re.M):
-    caps.setdefault(mm.group(1), []).append((int(mm.group(2)), int(mm.group(3))))
+  for e in jit.parse_specs(text):
+    caps.setdefault(e["scene"], []).append((e["dims"]["nconmax"], e["dims"]["njmax"]))
   assert caps["g1_tracking"] == [(56, 200), (48, 160), (250, 250)]
   for name in ("g1_velocity", "g1_jump", "g1_velocity_rough", "g1_jump_hfield"):
     assert caps[name] == [(48, 160), (300, 300)], name
