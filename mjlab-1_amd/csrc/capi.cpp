@@ -92,7 +92,7 @@ struct Capacity {
 };
 
 // The host part of a capacity; `too_big` is the refusal of a carve past a CU's LDS.
-static int make_capacity(const mjx::SpecKey& key, int neq, int max_condim, int cone,
+static int make_capacity(const mjx::SpecKey& key, int neq, int max_condim, int cone, int nellipsoid,
                          const char* too_big, Capacity& c) {
   const mjx::Dims& d = c.d = key.d;
   for (int i = 0; i < 3; i++) {
@@ -102,7 +102,7 @@ static int make_capacity(const mjx::SpecKey& key, int neq, int max_condim, int c
     c.lds[i] = mjx::make_lds(d, i, false, mjx::con_mu_width(max_condim), cone);
     if ((size_t)c.lds[i].total * 4 > 160 * 1024) return fail(too_big);
   }
-  c.spec = mjx::spec_can_hold(neq, max_condim, cone) ? mjx::find_spec(key) : 0;
+  c.spec = mjx::spec_can_hold(neq, max_condim, cone, nellipsoid) ? mjx::find_spec(key) : 0;
   c.gC = (c.lds[1].pack_len + 63) & ~63;
   c.gF = c.gC + ((c.lds[2].pack_len + 63) & ~63);
   c.gstride = c.gF + ((mjx::ltr_size((d.nv + 3) & ~3) + 63) & ~63);  // implicit factor, LTR form
@@ -366,7 +366,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   s->nworld = nworld;
   s->dm = model->dm;
   if (make_capacity(model->t.spec_key(nconmax, njmax), model->t.neq, model->t.max_condim, model->t.o.cone,
-                    "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
+                    model->t.nellipsoid, "per-world LDS footprint exceeds 160 KiB; lower njmax/nconmax", s->fast))
     return -1;
   // An elliptic model runs without Newton row classes: a class launch copies the pack's row
   // slots region by region into its smaller carve, and the grouping words (carve.h make_lds)
@@ -389,7 +389,7 @@ int mjx_sim_create_ex(const mjxModel* model, int nworld, int nconmax, int njmax,
   s->con_stride = s->has_big ? nconmax_max : nconmax;
   if (s->has_big) {
     if (make_capacity(model->t.spec_key(nconmax_max, njmax_max), model->t.neq, model->t.max_condim,
-                      model->t.o.cone, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
+                      model->t.o.cone, model->t.nellipsoid, "max-capacity LDS footprint exceeds 160 KiB; lower njmax_max/nconmax_max", s->big))
       return -1;
     // re-solve list capacity per split and substep parity: every world may be listed
     s->ovf_cap = nworld;

@@ -29,7 +29,8 @@ constexpr int kStaticChunk = 64; // terrain geoms per broadphase chunk
 
 enum { EFC_LIMIT = 0, EFC_FRICTIONLESS = 1, EFC_PYRAMIDAL = 2, EFC_EQUALITY = 3 };
 constexpr int kMaxEq = 64;       // equalities per world: one lane each in phase A's row count
-enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_CYLINDER = 5,
+enum { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_ELLIPSOID = 4,
+       GEOM_CYLINDER = 5,
        GEOM_BOX = 6 };
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
 enum { SENS_GYRO = 0, SENS_VELOCIMETER = 1, SENS_ACCELEROMETER = 2, SENS_SUBTREEANGMOM = 3,
@@ -193,16 +194,19 @@ inline bool operator==(const SpecKey& a, const SpecKey& b) {
   return memcmp(&a.d, &b.d, sizeof(Dims)) == 0 && a.ncyl == b.ncyl && a.npar == b.npar &&
          a.npar <= kMaxDof && memcmp(a.par, b.par, sizeof(int) * a.npar) == 0;
 }
-// What every specialisation leaves out: its kernels take these three as constants, so the
+// What every specialisation leaves out: its kernels take the first three as constants, so the
 // equality rows of phase A, the torsional / rolling contact rows (contact dimensions 4 and 6)
 // of phases A and C, and the elliptic cone's rows, solver and wrench decode fold away there.
+// Nor does any hold the ellipsoid narrowphase (engine_impl.h kEllipsoid: the generic kernels
+// only), so a specialisation holds no candidate pair with an ellipsoid geom.
 // A model with any of them runs the generic kernels (capi.cpp make_capacity;
 // mjlab_amd/jit.py ineligible is the same rule in Python).
 struct kSpecHolds {
-  static constexpr int neq = 0, max_condim = 3, cone = 0;
+  static constexpr int neq = 0, max_condim = 3, cone = 0, nellipsoid = 0;
 };
-constexpr bool spec_can_hold(int neq, int max_condim, int cone) {
-  return neq == kSpecHolds::neq && max_condim <= kSpecHolds::max_condim && cone == kSpecHolds::cone;
+constexpr bool spec_can_hold(int neq, int max_condim, int cone, int nellipsoid) {
+  return neq == kSpecHolds::neq && max_condim <= kSpecHolds::max_condim && cone == kSpecHolds::cone &&
+         nellipsoid == kSpecHolds::nellipsoid;
 }
 int find_spec(const SpecKey& key);
 // Specialisations compiled at run time (jit.hip, loaded by mjx_spec_register) get ids from

@@ -1688,6 +1688,171 @@ __device__ __noinline__ int cylinder_pair(const ConOut& co, int key, int g1, int
   return -1;
 }
 
+// --------------------------------------------------------------------------- ellipsoid
+// Ellipsoid narrowphase (geom type 4: semi-axes size[0..2] along its frame's axes).  The plane and
+// the sphere are closed form up to one scalar root; capsule, ellipsoid, cylinder and box partners
+// go through one more instantiation of convex_pair, over AnySupport below.  A strictly convex
+// shape touches another convex one in one point: every pair gives one contact.
+//
+// The nearest point x of the surface to p, shape frame, semi-axes s: p - x is along the surface
+// normal at x, x_i = s_i^2 p_i / (t + s_i^2), with t the largest root of the secular equation
+//   F(t) = sum_i (s_i p_i / (t + s_i^2))^2 - 1 = 0,
+// t >= 0 for p outside and t in (-s_min^2, 0) for p inside.  F is convex and decreasing right of
+// its last pole -s_min^2.  Solved in u = t + s_min^2 > 0 (the denominators u + e_i, e_i = s_i^2 -
+// s_min^2, lose nothing to cancellation next to the pole) from the left end of a bracket:
+//   lo = max_i (s_i |p_i| - e_i)  (every term alone is <= 1 there, the arg-max one equals 1, so
+//        F(lo) <= 2), and u >= s_min^2 outside;
+//   hi = |s o p| outside (every denominator >= u), s_min^2 inside.
+// The step is Newton's on phi = 1 - (F + 1)^(-1/2), which has F's root and sign, is convex and
+// decreasing too, and is a straight line for a single pole: from the left it rises monotonically
+// to the root and does not crawl (by 3/2 a step) where one pole dominates, as Newton on F does.
+// A step that leaves the bracket is replaced by its midpoint.  A fixed count, no early exit:
+// kEllOut steps outside (the error stops falling at 6 for axis ratios up to 10, at 8 for 100),
+// kEllIn inside, started at the pole's own estimate u = s_m |p_m| / sqrt(1 - rest) where that lies in
+// the bracket (a point next to a symmetry plane has its root a few |p_m| from the pole).
+//   fp32 accuracy, 10:1 axes (a, a, c): F is a sum of three squares near 1, good to eF ~ 2e-7; the
+// root moves by eF / |F'| with |F'| >= 2 y_c^2 / (u + e_c), y = x / s, so the short-axis
+// coordinate c y_c moves by at most (a / c) / 2 . c eF and the long ones by a eF / 2: 1e-8 m and
+// 1e-8 m for the disc (0.1, 0.1, 0.01) -- the same size as the rounding of p itself in the shape
+// frame (|p| 2^-24).  The cost of a thin shape is iterations, not digits.
+constexpr int kEllOut = 8;
+constexpr int kEllIn = 16;
+__device__ __forceinline__ V3 had(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+// surface = false: the point of the solid nearest p (p itself when inside); true: the point of
+// the surface nearest p, also for p inside.  At the centre and on the smallest axis' symmetry
+// plane inside (p_m = 0: no bracket from lo) the stationary point of the pole itself, the long
+// axes' coordinates at u = 0 and the smallest axis' from the surface equation -- while that point
+// exists, sum_{i != m} (s_i p_i / e_i)^2 <= 1.  Past that (p_m = 0 near the rim) the nearest point
+// lies in the plane too: the m-term is dropped and the root u > 0 of the rest is iterated.
+// Out of line: inlined into convex_pair's projection rounds its registers are added to that routine's
+// live set (profiles/ellipsoid_kernel_resources.txt: the generic network-actuator kernels at 256 VGPRs).
+__device__ __noinline__ V3 ell_nearest(V3 s, V3 p, bool surface) {
+  const V3 ps = {p.x / s.x, p.y / s.y, p.z / s.z};
+  const float q = dot(ps, ps);
+  if (q <= 1.f && !surface) return p;
+  const int m = s.x <= s.y && s.x <= s.z ? 0 : (s.y <= s.z ? 1 : 2);
+  const float sm = vc(s, m);
+  const V3 s2 = had(s, s);
+  V3 y = {s.x * fabsf(p.x), s.y * fabsf(p.y), s.z * fabsf(p.z)};
+  const V3 e = {(s.x - sm) * (s.x + sm), (s.y - sm) * (s.y + sm), (s.z - sm) * (s.z + sm)};
+  float lo = fmaxf(fmaxf(y.x - e.x, y.y - e.y), y.z - e.z), hi, u;
+  if (q > 1.f) {
+    lo = fmaxf(lo, sm * sm);
+    hi = fmaxf(lo, norm(y));
+    u = lo;
+  } else {
+    hi = sm * sm;
+    if (lo <= 1e-20f) {
+      V3 x = {e.x > 1e-6f * s2.x ? s2.x * p.x / e.x : p.x, e.y > 1e-6f * s2.y ? s2.y * p.y / e.y : p.y,
+              e.z > 1e-6f * s2.z ? s2.z * p.z / e.z : p.z};
+      const V3 xs = {m == 0 ? 0.f : x.x / s.x, m == 1 ? 0.f : x.y / s.y, m == 2 ? 0.f : x.z / s.z};
+      const float rm = 1.f - dot(xs, xs);
+      if (rm >= 0.f) {
+        const float xm = copysignf(sm * sqrtf(rm), vc(p, m));
+        if (m == 0) x.x = xm; else if (m == 1) x.y = xm; else x.z = xm;
+        return x;
+      }
+      if (m == 0) y.x = 0.f; else if (m == 1) y.y = 0.f; else y.z = 0.f;
+      lo = 1e-12f * hi;  // (F(0+) = -rm > 0; not 0 itself: an axis tied with the smallest has e_i = 0)
+    }
+    u = lo;
+    const V3 w = {y.x / (lo + e.x), y.y / (lo + e.y), y.z / (lo + e.z)};
+    const float wm = vc(w, m), rest = dot(w, w) - wm * wm;
+    const float u0 = vc(y, m) / sqrtf(fmaxf(1.f - rest, 1e-30f));
+    if (rest < 1.f && u0 > lo && u0 < hi) u = u0;
+  }
+  const int iters = q > 1.f ? kEllOut : kEllIn;
+  for (int it = 0; it < iters; it++) {
+    const V3 a = {1.f / (u + e.x), 1.f / (u + e.y), 1.f / (u + e.z)};
+    const V3 w = had(y, a), w2 = had(w, w);
+    const float N = w2.x + w2.y + w2.z, dN = -2.f * dot(w2, a);
+    if (N > 1.f) lo = u; else hi = u;
+    const float un = u - 2.f * N * (sqrtf(N) - 1.f) / dN;
+    u = un >= lo && un <= hi ? un : 0.5f * (lo + hi);  // (false for a NaN step too)
+  }
+  return {s2.x * p.x / (u + e.x), s2.y * p.y / (u + e.y), s2.z * p.z / (u + e.z)};
+}
+// Plane (geom g1: point pp, normal n) against the ellipsoid (centre c, frame R, semi-axes s),
+// MuJoCo's mjc_PlaneEllipsoid restated: with l = R^T n the support height along n is |s o l|, the
+// lowest point is the support along -n, the position midway to the plane as plane_sphere.
+__device__ __forceinline__ int plane_ellipsoid(const ConOut& co, int key, int g1, int g2, V3 pp, V3 n,
+                                               V3 c, const float* R, V3 s, float margin) {
+  const V3 sl = had(s, mulTv(R, n));
+  const float h = fmaxf(norm(sl), MINVAL);
+  const float dist = dot(n, c - pp) - h;
+  if (dist > margin) return 0;
+  append(co, key, g1, g2, dist, c - mulv(R, had(s, sl)) * (1.0f / h) - n * (0.5f * dist), n);
+  return 1;
+}
+// Sphere (geom g1, centre `loc` in the ellipsoid's frame F, radius rs) against the ellipsoid (geom
+// g2): the surface point q nearest the centre, dist = +-|loc - q| - rs, normal from the sphere to
+// the ellipsoid as sphere_cylinder: q - loc outside, loc - q inside -- both the inward surface normal
+// at q, which stands in where the centre is within a tenth of the smallest axis of the surface
+// (the difference of two nearby points loses the direction; the gradient does not).
+__device__ __forceinline__ int sphere_ellipsoid(const ConOut& co, int key, int g1, int g2, const HFrame& F,
+                                                V3 s, V3 loc, float rs, float margin) {
+  const V3 ls = {loc.x / s.x, loc.y / s.y, loc.z / s.z};
+  const bool inside = dot(ls, ls) <= 1.f;
+  const V3 q = ell_nearest(s, loc, true);
+  const V3 dv = inside ? loc - q : q - loc;
+  const float len = norm(dv);
+  if (!inside && len - rs > margin) return 0;
+  const V3 g = {q.x / (s.x * s.x), q.y / (s.y * s.y), q.z / (s.z * s.z)};
+  const V3 n = len > 0.1f * fminf(s.x, fminf(s.y, s.z)) ? dv * (1.0f / len)
+                                                        : g * (-1.0f / fmaxf(norm(g), 1e-30f));
+  const float cd = (inside ? -len : len) - rs;
+  // midway between the sphere's point loc + n rs and q
+  append(co, key, g1, g2, cd, F.p + mulv(F.R, (loc + n * rs + q) * 0.5f), mulv(F.R, n));
+  return 1;
+}
+// Any of the four convex solids an ellipsoid meets through convex_pair, by geom kind: one support
+// type, so that all those pairs share ONE instantiation of that (large, out-of-line) routine
+// instead of four.  Capsule: the segment |z| <= size[1] swept by the radius size[0].
+struct AnySupport {
+  int kind;
+  V3 s;
+  __device__ __forceinline__ V3 operator()(V3 d) const {
+    if (kind == GEOM_ELLIPSOID) {
+      const V3 sd = had(s, d);
+      const float l = norm(sd);
+      return l > 1e-20f ? had(s, sd) * (1.0f / l) : V3{0.f, 0.f, 0.f};
+    }
+    if (kind == GEOM_CAPSULE) {
+      const float l = norm(d), k = l > 1e-20f ? s.x / l : 0.f;
+      return {d.x * k, d.y * k, d.z * k + (d.z >= 0.f ? s.y : -s.y)};
+    }
+    if (kind == GEOM_CYLINDER) return CylSupport{s.x, s.y}(d);
+    return BoxSupport{s}(d);
+  }
+  __device__ __forceinline__ V3 proj(V3 p) const {
+    if (kind == GEOM_ELLIPSOID) return ell_nearest(s, p, false);
+    if (kind == GEOM_CAPSULE) {
+      const V3 v = {p.x, p.y, p.z - fminf(fmaxf(p.z, -s.y), s.y)};
+      const float l = norm(v);
+      return l > s.x ? p - v * (1.f - s.x / l) : p;
+    }
+    if (kind == GEOM_CYLINDER) return CylSupport{s.x, s.y}.proj(p);
+    return BoxSupport{s}.proj(p);
+  }
+};
+// Every pair with an ellipsoid (types t1 <= t2, frames F1 / F2, sizes s1 / s2), out of line as
+// cylinder_pair.  -1: a pair kind without a routine (hfield, mesh: the caller raises the
+// unsupported-pair flag).
+__device__ __noinline__ int ellipsoid_pair(const ConOut& co, int key, int g1, int g2, int t1, int t2,
+                                           const HFrame& F1, const float* s1, const HFrame& F2,
+                                           const float* s2, float margin) {
+  if (t2 == GEOM_ELLIPSOID) {
+    if (t1 == GEOM_PLANE)
+      return plane_ellipsoid(co, key, g1, g2, F1.p, V3{F1.R[2], F1.R[5], F1.R[8]}, F2.p, F2.R, v3(s2), margin);
+    if (t1 == GEOM_SPHERE)
+      return sphere_ellipsoid(co, key, g1, g2, F2, v3(s2), mulTv(F2.R, F1.p - F2.p), s1[0], margin);
+    if (t1 != GEOM_CAPSULE && t1 != GEOM_ELLIPSOID) return -1;
+  } else if (t1 != GEOM_ELLIPSOID || (t2 != GEOM_CYLINDER && t2 != GEOM_BOX)) {
+    return -1;
+  }
+  return convex_pair(co, key, g1, g2, F1, AnySupport{t1, v3(s1)}, F2, AnySupport{t2, v3(s2)}, margin);
+}
+
 // --------------------------------------------------------------------------- impedance
 __device__ __forceinline__ float impedance(const float* si, float pos, float margin) {
   float dmin = fminf(MAXIMP, fmaxf(MINIMP, si[0])), dmax = fminf(MAXIMP, fmaxf(MINIMP, si[1]));
@@ -1869,6 +2034,9 @@ template <int SP> constexpr bool kBoxBox = SP == 0 || Spec<SP>::dims().nboxbox >
 // cylinder narrowphase compiled in: the generic kernels, and a run-time specialisation of a model
 // with cylinder pairs
 template <int SP> constexpr bool kCylinder = SP == 0 || Spec<SP>::ncyl > 0;
+// ellipsoid narrowphase compiled in: the generic kernels only (a model with ellipsoid pairs never
+// selects a specialisation: engine.h spec_can_hold)
+template <int SP> constexpr bool kEllipsoid = SP == 0;
 // at most one contact per lane of the world's wave (every fast carve, nconmax <= 64): the
 // contact loops of phases A and C are then the single lane-per-contact pass; a max carve past
 // 64 contacts (sim.max_capacity: the reference's njmax bounds a world's contacts too) takes
@@ -3673,7 +3841,13 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
         const float* s1 = gsize + 3 * g1;
         const float* s2 = gsize + 3 * g2;
         int key = p * 8;
-        if (kCylinder<SP> && (t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER)) {
+        if (kEllipsoid<SP> && (t1 == GEOM_ELLIPSOID || t2 == GEOM_ELLIPSOID)) {
+          // (type 4 sorts before the cylinder's 5: ellipsoid-cylinder is an ellipsoid pair)
+          HFrame F1, F2;
+          F1.p = p1; F2.p = p2;
+          for (int i = 0; i < 9; i++) { F1.R[i] = S[L.gxmat + 9 * l1 + i]; F2.R[i] = S[L.gxmat + 9 * l2 + i]; }
+          if (ellipsoid_pair(co, key, g1, g2, t1, t2, F1, s1, F2, s2, margin) < 0) atomicOr(&ints[3], 4);
+        } else if (kCylinder<SP> && (t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER)) {
           // every cylinder pair behind one call: the loop keeps its registers (as box_box)
           HFrame F1, F2;
           F1.p = p1; F2.p = p2;
@@ -3837,6 +4011,11 @@ __device__ __forceinline__ void step_body(float* __restrict__ S, const Params* _
                     Fp.p = p1;
                     for (int i = 0; i < 9; i++) Fp.R[i] = S[L.gxmat + 9 * l1 + i];
                     cylinder_pair(co, key, g1, sg, GEOM_CYLINDER, GEOM_BOX, Fp, s1, F, gsize + 3 * sg, margin);
+                  } else if (kEllipsoid<SP> && t1 == GEOM_ELLIPSOID) {
+                    HFrame Fp;
+                    Fp.p = p1;
+                    for (int i = 0; i < 9; i++) Fp.R[i] = S[L.gxmat + 9 * l1 + i];
+                    ellipsoid_pair(co, key, g1, sg, GEOM_ELLIPSOID, GEOM_BOX, Fp, s1, F, gsize + 3 * sg, margin);
                   } else {
                     atomicOr(&ints[3], 4);
                   }

@@ -25,6 +25,8 @@ struct ModelTables {
   int neq = 0;     // joint equalities (fields.h counts the eq_* fields by it)
   int max_condim = 3;  // largest geom_condim, at least 3 (check_condims; engine.h DModel::max_condim)
   int ncylinder = 0;  // candidate pairs with a cylinder geom
+  int nellipsoid = 0;  // candidate pairs with an ellipsoid geom: such a model runs the generic
+                       // kernels (engine.h spec_can_hold; not in SpecKey: no entry holds the code)
   int ncsens = 0;  // 0 past 64 single-slot contact sensors (phase C then matches serially)
   std::vector<int32_t> dof_parentid;  // as given
   // what selects the specialised kernels of a sim of this model at a capacity (engine.h SpecKey)
@@ -317,11 +319,12 @@ inline std::string terrain_blocks(const mjxModelDesc& desc, ModelTables& t) {
   d.npair = nreg;
   d.npair_all = np;
   d.nboxbox = 0;
-  t.ncylinder = 0;
+  t.ncylinder = t.nellipsoid = 0;
   for (int q = 0; q < np; q++) {
     const int t1 = desc.geom_type[desc.pair_geom1[q]], t2 = desc.geom_type[desc.pair_geom2[q]];
     d.nboxbox += t1 == GEOM_BOX && t2 == GEOM_BOX;
     t.ncylinder += t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER;
+    t.nellipsoid += t1 == GEOM_ELLIPSOID || t2 == GEOM_ELLIPSOID;
   }
   d.nstatic = (int)t.st_geom.size();
   d.nstpartner = (int)t.st_partner.size();

@@ -155,8 +155,8 @@ def library_path(model, nconmax: int, njmax: int, role: int) -> tuple[str, str, 
 
 def ineligible(model) -> str | None:
   """Why no specialised kernel can run `model` (None: one can).  The rule of csrc/engine.h
-  spec_can_hold: specialised kernels hold no equality rows, no torsional or rolling contact rows
-  and no elliptic cone, so such a model runs the generic kernels only."""
+  spec_can_hold: specialised kernels hold no equality rows, no torsional or rolling contact rows,
+  no elliptic cone and no ellipsoid narrowphase, so such a model runs the generic kernels only."""
   if len(model.arrays.get("eq_type", ())) > 0:
     return "a model with equality constraints runs the generic kernels only " \
            "(equalities are not compiled into specialised or JIT kernels)"
@@ -167,6 +167,12 @@ def ineligible(model) -> str | None:
   if int(getattr(model, "cone", 0)) != 0:
     return "a model with elliptic friction cones runs the generic kernels only " \
            "(the cone rows and solver are not compiled into specialised or JIT kernels)"
+  # (candidate pairs with a geom of type 4: csrc/model_tables.h ModelTables::nellipsoid)
+  gt = np.asarray(model.arrays.get("geom_type", ())).reshape(-1)
+  p1, p2 = (np.asarray(model.arrays.get(k, ()), dtype=np.int64).reshape(-1) for k in ("pair_geom1", "pair_geom2"))
+  if len(p1) and bool(((gt[p1] == 4) | (gt[p2] == 4)).any()):
+    return "a model with ellipsoid geoms in its collision pairs runs the generic kernels only " \
+           "(the ellipsoid narrowphase is not compiled into specialised or JIT kernels)"
   return None
 
 
