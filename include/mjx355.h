@@ -319,6 +319,52 @@ typedef struct mjxActuatorNetDesc {
 size_t mjx_actuator_net_desc_size(void);
 int mjx_sim_set_actuator_nets(mjxSim* sim, const mjxActuatorNetDesc* desc, void* stream);
 
+/* Rollout-time policy evaluation (mjlab_amd/rl/fused_policy.py: FusedPolicy): the actor and
+ * critic MLPs of rsl_rl's ActorCritic, the Gaussian draw and its log-probability in one
+ * launch (csrc/policy.hip), no sim involved.  Per network, for every row i < n:
+ *   x = obs[i, :width[0]], normalised (x - norm_mean) / (norm_std + norm_eps) where norm_mean
+ *   is not null;  x <- activation(W_l x + b_l) for l < nlayer - 1;  y = W_last x + b_last
+ * (fp32 accumulation on the matrix cores).  weight[l] is device [width[l + 1], width[l]]
+ * row-major (torch's nn.Linear.weight), bias[l] device [width[l + 1]].  Limits: 1..5 layers,
+ * width[0] in [1, 1024], every hidden width in [1, 512], the actor's output in [1, 64], the
+ * critic's output 1; a critic with nlayer 0 is not evaluated.  activation: 0 none, 1 relu,
+ * 2 elu (alpha 1), 3 tanh.  Then, with mu = the actor's y and sigma = std (exp(std) when
+ * std_is_log), both [width[nlayer]]:
+ *   a = mu + sigma * eps;  log_prob = sum_j (-(a_j - mu_j)^2 / (2 sigma_j^2) - log sigma_j
+ *   - log sqrt(2 pi));  value = the critic's y
+ * eps is device [n, na] standard normals of the caller's.  A null eps means no draw: only the
+ * actor runs and only mu is written.  Outputs are device rows of *_stride floats each; a null
+ * output is not written.  Every pointer is dereferenced by the kernel, not by this call: the
+ * descriptor can point at the live parameters, and an optimiser step is seen by the next call.
+ * Stream-ordered, never synchronises, capturable.  Anything outside the limits (also a null
+ * weight, n <= 0, a pointer that is not 4-byte aligned) returns -1 with mjx_last_error set
+ * and launches nothing. */
+#define MJX_POLICY_MAX_LAYERS 5
+typedef struct mjxPolicyNet {
+  int32_t nlayer;
+  int32_t activation;
+  int32_t width[MJX_POLICY_MAX_LAYERS + 1];
+  int32_t obs_stride;        /* floats between observation rows, >= width[0] */
+  float norm_eps;
+  const float* weight[MJX_POLICY_MAX_LAYERS];
+  const float* bias[MJX_POLICY_MAX_LAYERS];
+  const float* obs;          /* [n, obs_stride] */
+  const float* norm_mean;    /* [width[0]] or null: no normalisation */
+  const float* norm_std;     /* [width[0]] */
+} mjxPolicyNet;
+typedef struct mjxPolicyDesc {
+  int32_t n;
+  int32_t std_is_log;
+  mjxPolicyNet actor, critic;
+  const float* std;          /* [na] */
+  const float* eps;          /* [n, na] or null */
+  float *actions, *values, *log_prob, *mu, *sigma;  /* [n, na | 1 | 1 | na | na] rows */
+  int32_t actions_stride, values_stride, log_prob_stride, mu_stride, sigma_stride;
+  int32_t reserved;
+} mjxPolicyDesc;
+size_t mjx_policy_desc_size(void);
+int mjx_policy_act(const mjxPolicyDesc* desc, void* stream);
+
 /* Diagnostics: per-sim counters as int32[8] written to host `out` ([0] max contacts, [1] max
  * rows seen, [2] contact-overflow, [3] row-overflow, [4] unsupported-pair events -- dropped
  * work --, [5] max Newton iterations, [6] worlds re-solved at the max capacity); synchronises

@@ -19,6 +19,7 @@
 #include "../../include/mjx355.h"
 #include "engine.h"
 #include "model_tables.h"
+#include "policy.h"
 
 // ---------------------------------------------------------------- minimal DLPack ABI
 extern "C" {
@@ -260,6 +261,14 @@ extern "C" {
 const char* mjx_last_error(void) { return g_err.c_str(); }
 int mjx_abi_version(void) { return MJX_ABI_VERSION; }
 size_t mjx_model_desc_size(void) { return sizeof(mjxModelDesc); }
+
+// the rollout policy (csrc/policy.hip): no handle, one launch per call
+size_t mjx_policy_desc_size(void) { return sizeof(mjxPolicyDesc); }
+int mjx_policy_act(const mjxPolicyDesc* desc, void* stream) {
+  std::string err;
+  if (mjx::policy_act(desc, (hipStream_t)stream, &err) != 0) return fail(err);
+  return 0;
+}
 
 int mjx_model_create(const mjxModelDesc* desc, int device, mjxModel** out) {
   if (!desc || !out) return fail("null argument");

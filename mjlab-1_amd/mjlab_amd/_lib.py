@@ -23,6 +23,8 @@ EXPORTS = ("mjx_last_error", "mjx_abi_version", "mjx_model_desc_size", "mjx_mode
            "mjx_sim_info", "mjx_sim_mass_matrix", "mjx_spec_register", "mjx_launch_counts",
            "mjx_launch_counts_reset", "mjx_sim_set_actuators", "mjx_actuator_desc_size",
            "mjx_sim_set_actuator_nets", "mjx_actuator_net_desc_size", "mjx_sensor_launch_count",
+           # the rollout policy kernel (bound in rl/fused_policy.py)
+           "mjx_policy_desc_size", "mjx_policy_act",
            # include/mjx355_task.h (fused velocity-task managers; bound in fused.py)
            "mjx_task_create", "mjx_task_destroy", "mjx_task_action", "mjx_task_substep",
            "mjx_task_post", "mjx_task_reset", "mjx_task_observe", "mjx_task_desc_size",
@@ -103,7 +105,8 @@ def lib() -> ctypes.CDLL:
     if name.startswith(("mjx_task_", "mjx_track_")):
       continue  # bound by mjlab_amd.fused / mjlab_amd.fused_tracking
     if name not in ("mjx_last_error", "mjx_field_name", "mjx_model_desc_size",
-                    "mjx_actuator_desc_size", "mjx_actuator_net_desc_size"):
+                    "mjx_actuator_desc_size", "mjx_actuator_net_desc_size",
+                    "mjx_policy_desc_size"):
       getattr(L, name).restype = ci
   from ._capi import ABI_VERSION
   if L.mjx_abi_version() != ABI_VERSION:

@@ -200,7 +200,8 @@ class PPO:
   def __init__(self, policy: ActorCritic, num_learning_epochs=5, num_mini_batches=4, clip_param=0.2,
                gamma=0.99, lam=0.95, value_loss_coef=1.0, entropy_coef=0.01, learning_rate=1e-3,
                max_grad_norm=1.0, use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01,
-               device="cpu", normalize_advantage_per_mini_batch=False, multi_gpu=False, **_):
+               device="cpu", normalize_advantage_per_mini_batch=False, multi_gpu=False,
+               fused_act: bool = False, **_):
     self.device = device
     self.policy = policy.to(device)
     self.learning_rate = learning_rate
@@ -216,6 +217,10 @@ class PPO:
     self.storage: RolloutStorage | None = None
     self.graph_act = True  # GPU: rollout-time policy evaluation as one graph replay
     self._act_graph = self._act_key = self._gobs = self._gout = None
+    # GPU: the same evaluation as one HIP kernel writing into the rollout storage
+    # (rl/fused_policy.py); takes precedence over graph_act
+    self.fused_act = fused_act
+    self._fused = self._feps = None
 
   def init_storage(self, num_envs: int, num_transitions: int, obs: dict, num_actions: int):
     self.storage = RolloutStorage(num_envs, num_transitions, obs, num_actions, self.device)
@@ -234,6 +239,8 @@ class PPO:
     s, t = self.storage, self.storage.step
     for k, v in obs.items():  # the env's graph outputs are overwritten by the next step
       s.observations[k][t].copy_(v)
+    if self.fused_act and torch.device(self.device).type == "cuda":
+      return self._act_fused(obs)
     if self.graph_act and torch.device(self.device).type == "cuda":
       out = self._act_graphed(obs)
     else:
@@ -241,6 +248,19 @@ class PPO:
     for dst, src in zip((s.actions, s.values, s.actions_log_prob, s.mu, s.sigma), out):
       dst[t].copy_(src)
     return out[0]
+
+  def _act_fused(self, obs: dict) -> torch.Tensor:
+    """The rollout-time policy evaluation as one kernel launch (FusedPolicy): the standard
+    normals are drawn as on the graphed path, and the kernel writes actions, values,
+    log-probabilities, means and standard deviations into row t of the storage itself."""
+    s, t = self.storage, self.storage.step
+    if self._fused is None:
+      from .fused_policy import FusedPolicy
+      self._fused = FusedPolicy(self.policy)
+      self._feps = torch.zeros(s.N, s.actions.shape[-1], device=self.device)
+    self._feps.normal_()
+    self._fused.act(obs, self._feps, s.actions[t], s.values[t], s.actions_log_prob[t], s.mu[t], s.sigma[t])
+    return s.actions[t]
 
   def _act_graphed(self, obs: dict):
     """The rollout-time policy evaluation (actor + critic MLPs, action draw, log-prob) as

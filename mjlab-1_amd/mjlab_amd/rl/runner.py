@@ -191,8 +191,12 @@ class OnPolicyRunner:
       self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
     self.current_learning_iteration = int(d["iter"])
 
-  def get_inference_policy(self, device: str | None = None):
+  def get_inference_policy(self, device: str | None = None, fused: bool = False):
+    """`fused`: the actor as one HIP kernel launch (rl/fused_policy.py) instead of torch."""
     self.alg.policy.eval()
     if device is not None:
       self.alg.policy.to(device)
+    if fused:
+      from .fused_policy import FusedPolicy
+      return FusedPolicy(self.alg.policy).act_inference
     return self.alg.policy.act_inference
